@@ -24,6 +24,13 @@ Other BASELINE configs run through the same harness:
 
 Rank 0 prints exactly one JSON line with the whole-job aggregate
 samples/sec (sum over all clients).
+
+A plain run does only what that line needs: set up, warm up, time the K
+rounds, print. ``--dump-outputs DIR`` additionally writes the last round's
+results (loss + model arena) as ``DIR/<name>.npy`` so two builds can be
+compared output for output: model init and data are seeded, so the inputs
+are identical from run to run. ``--full`` is where any secondary
+measurement belongs; there is none today.
 """
 
 from __future__ import annotations
@@ -66,7 +73,55 @@ def parse_args():
                         "graph-capturable models; single-minibatch capture "
                         "measured slower than eager and was replaced)")
     p.add_argument("--no-hip-graph", dest="hip_graph", action="store_false")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last round "
+                        "produced (loss + the client's model arena) as "
+                        "DIR/<name>.npy in float32, <= 64 MB in all")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement/check; a "
+                        "plain run does only what the headline needs (this "
+                        "benchmark has no secondary work, so --full "
+                        "currently adds nothing)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if args.warmup < 0:
+        p.error("--warmup must be >= 0")
+    return args
+
+
+# --dump-outputs budget: float32 elements over all files (60 MB of payload,
+# leaving headroom under the 64 MB cap for the .npy headers)
+_DUMP_MAX_ELEMS = 15 * 1024 * 1024
+_DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir, last_loss, arena):
+    """Write the arrays a caller of one federated round receives — the last
+    minibatch loss and the (aggregated) model arena, one file per dtype
+    group — as float32 .npy. An arena larger than the budget is cut down to
+    a fixed, seeded sample of its elements (same indices on every run), the
+    budget shared among the groups in proportion to their size."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    if last_loss is not None:
+        np.save(os.path.join(out_dir, "loss.npy"),
+                last_loss.detach().float().reshape(1).cpu().numpy())
+    named = [(f"params_{str(g.dtype).split('.')[-1]}", g.flat)
+             for g in arena.groups]
+    named += [(f"buffers_{str(g.dtype).split('.')[-1]}", g.flat)
+              for g in arena.buffer_groups]
+    total = sum(t.numel() for _, t in named)
+    gen = torch.Generator(device="cpu").manual_seed(_DUMP_SAMPLE_SEED)
+    for name, flat in named:
+        t = flat.detach()
+        if total > _DUMP_MAX_ELEMS:
+            keep = max(1, t.numel() * _DUMP_MAX_ELEMS // total)
+            idx = torch.randint(0, t.numel(), (keep,), generator=gen)
+            t = t[idx.sort().values.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"),
+                t.float().cpu().numpy())
 
 
 MODEL_DEFAULTS = {
@@ -294,6 +349,12 @@ def main():
                          device=plane._coll_device())
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs:
+        if plane is not None and plane.pending is not None:
+            plane.pending.wait()  # fence the last round's aggregation
+        if rank == 0:  # after FedAvg every rank holds the same model
+            dump_outputs(args.dump_outputs, last_loss, arena)
 
     samples_per_round = (n_local // bs) * bs  # tail batch dropped
     rounds_per_sec = args.steps / elapsed

@@ -34,15 +34,59 @@ def test_bench_json_contract(tmp_path):
     assert "global_batch" in d["config"] and "parallelism" in d["config"]
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last round's loss + model arena as float32
+    .npy (<= 64 MB in all), consistent with the JSON line; --full is
+    accepted and leaves the result line's contract unchanged."""
+    import numpy as np
+
+    env = dict(os.environ)
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env["PYTHONPATH"] = repo
+    out = tmp_path / "dump"
+    proc = subprocess.run(
+        [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1",
+         "--model", "llama-tiny", "--steps", "2", "--warmup", "0",
+         "--local-samples", "8", "--batch-size", "8", "--full",
+         "--dump-outputs", str(out)],
+        env=env, capture_output=True, text=True, timeout=600,
+    )
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, f"exactly one JSON line expected: {proc.stdout}"
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert d["metric"] == "fed_local_samples_per_sec"
+    files = sorted(p.name for p in out.iterdir())
+    assert "loss.npy" in files and any(f.startswith("params_") for f in files)
+    total = 0
+    for f in files:
+        a = np.load(out / f)
+        assert a.dtype == np.float32 and a.size > 0, f
+        assert np.isfinite(a).all(), f
+        total += (out / f).stat().st_size
+    assert total <= 64 * 1024 * 1024
+    loss = np.load(out / "loss.npy")
+    assert loss.shape == (1,)
+    assert abs(float(loss[0]) - d["config"]["last_loss"]) <= 1e-6 * max(
+        1.0, abs(d["config"]["last_loss"]))
+
+
 def test_bench_world2_driver_launch_shape():
     """The driver's exact multi-rank form: torch.distributed.run
     --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 bench.py
     --gpus 2. On CPU this runs the gloo data plane with a real 2-rank
     aggregation, per-rank Dirichlet shards, MAX-over-ranks timing, and
-    must print exactly ONE JSON line (rank 0) with the whole-job value."""
+    must print exactly ONE JSON line (rank 0) with the whole-job value.
+    With fewer than 2 GPUs visible a 2-rank RCCL world cannot form (one
+    rank per GPU), so the ranks are kept on the CPU/gloo path there."""
+    import torch
+
     env = dict(os.environ)
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env["PYTHONPATH"] = repo
+    if torch.cuda.is_available() and torch.cuda.device_count() < 2:
+        env["HIP_VISIBLE_DEVICES"] = "-1"  # no device index matches: CPU
     proc = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",

@@ -1,8 +1,10 @@
 // torch bindings for the baton_amd gfx950 kernels.
 //
-// Thin layer: validate tensors (contiguous, dtype, device), pull raw
-// pointers and the current HIP stream, call the launchers (launchers.h).
-// No compute here — every FLOP is in the .hip kernels.
+// Validate tensors (contiguous, dtype, device), allocate outputs and
+// workspaces, pull raw pointers and the current HIP stream, call the
+// launchers (launchers.h). Every FLOP is in the .hip kernels; the one
+// piece of policy executed here is the GEMM plan (gemm_plan.h): gemm()
+// allocates what the plan asks for and launches what it names.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -21,15 +23,46 @@ void check_compute(const at::Tensor& t, const char* name) {
 
 hipStream_t stream() { return at::hip::getCurrentHIPStream().stream(); }
 
-// NN dgrad routing: below this many B bytes the native NN staging beats a
-// transpose-to-NT pass (measured on BERT-base dgrad shapes); overridable
-// for A/B runs via BATON_NN_TRANSPOSE_BYTES.
-long long nn_transpose_bytes() {
-  static long long v = [] {
-    const char* e = std::getenv("BATON_NN_TRANSPOSE_BYTES");
-    return e ? std::atoll(e) : (long long)(1 << 20);
-  }();
-  return v;
+// Execute a plan_dense() plan: the 2-phase kernel, or G9 plus (ragged M)
+// the remainder rows under their own plan.
+void run_dense(const GemmProblem& p, const GemmPlan& pl, const void* A,
+               const void* B, void* C, const float* bias, long long strideA = 0,
+               long long strideB = 0, long long strideC = 0, int b_group = 1,
+               GemmStrides gs = GemmStrides{0, 0, 0, 1, 0, 0, 0}) {
+  if (pl.kind == GemmKind::G9) {
+    TORCH_CHECK(launch_gemm_nt_g9(pl, A, B, C, bias, pl.m_main, p.N, p.K,
+                                  (float)p.alpha, stream()),
+                "gemm: G9 plan does not fit ", pl.m_main, "x", p.N, "x", p.K);
+    if (pl.m_main == p.M) return;
+    const GemmProblem r = gemm_remainder(p, pl);
+    run_dense(r, plan_dense(r),
+              (const at::BFloat16*)A + (long long)pl.m_main * p.K, B,
+              (at::BFloat16*)C + (long long)pl.m_main * p.N, bias);
+    return;
+  }
+  TORCH_CHECK(launch_gemm_2ph(pl, p, A, B, C, bias, strideA, strideB, strideC,
+                              stream(), b_group, gs),
+              "gemm: 2-phase plan does not fit ", p.M, "x", p.N, "x", p.K);
+}
+
+// The split-K executors gemm() and the 1x1 conv wgrad share. A, B are NT
+// operands; out is [M, N], for the atomic route fp32 and zeroed.
+void run_slab(const GemmPlan& pl, const at::Tensor& A, const at::Tensor& B,
+              at::Tensor& out, int M, int N, int K) {
+  auto slabs = at::empty({(long long)pl.splits * M * N},
+                         A.options().dtype(at::kFloat));
+  TORCH_CHECK(launch_gemm_nt_slab(pl, A.data_ptr(), B.data_ptr(),
+                                  slabs.data_ptr<float>(), out.data_ptr(),
+                                  out.scalar_type() != at::kFloat, M, N, K,
+                                  stream()),
+              "gemm: slab plan does not fit ", M, "x", N, "x", K);
+}
+
+void run_splitk(const GemmPlan& pl, const at::Tensor& A, const at::Tensor& B,
+                at::Tensor& out, int M, int N, int K) {
+  TORCH_CHECK(launch_gemm_2ph_splitk(pl, is_bf16(A), A.data_ptr(), B.data_ptr(),
+                                     out.data_ptr<float>(), M, N, K, stream()),
+              "gemm: split-K plan does not fit ", M, "x", N, "x", K);
 }
 
 }  // namespace
@@ -395,74 +428,66 @@ at::Tensor gemm(at::Tensor A, at::Tensor B, int64_t layout,
                 "bias must be fp32 [N]");
     bias_ptr = bias.data_ptr<float>();
   }
-  // ---- dispatch (see gemm.hip header): the glds NT path is the fast one,
-  // so big transposed operands are re-laid-out once; small-tile long-K
-  // cases split the contraction over grid.z with fp32 accumulation.
-  // `direct` skips the transpose-to-NT re-layouts (split-K still applies):
-  // for a skinny-M NN like the LoRA dB^T (= xa^T @ dz), transposing the
-  // big [tokens, out] upstream grad costs more than the NT gain.
-  const bool plain = (beta == 0.0 && bias_ptr == nullptr && !relu);
-  at::Tensor Au = A, Bu = B;   // operands in NT orientation when routed
-  int eff_layout = (int)layout;
-  if (!direct && plain && layout == 2 && !out_f32) {
-    // TN -> NT: transpose both (any shape; bounds handled by staging)
-    auto At = at::empty({M, K}, A.options());
-    auto Bt = at::empty({N, K}, B.options());
-    launch_transpose(is_bf16(A), A.data_ptr(), At.data_ptr(), K, M, stream());
-    launch_transpose(is_bf16(B), B.data_ptr(), Bt.data_ptr(), K, N, stream());
-    Au = At; Bu = Bt; eff_layout = 0;
-  } else if (!direct && plain && layout == 1 &&
-             (long long)B.numel() * B.element_size() >= nn_transpose_bytes()) {
-    // big NN: transpose B -> NT
-    auto Bt = at::empty({N, K}, B.options());
-    launch_transpose(is_bf16(B), B.data_ptr(), Bt.data_ptr(), K, N, stream());
-    Bu = Bt; eff_layout = 0;
+  const GemmProblem p{is_bf16(A), out_f32, (int)layout, M, N, K,
+                      bias_ptr != nullptr, relu, alpha, beta, direct, 1, false};
+  const GemmPlan pl = plan_gemm(p);
+  at::Tensor Au = A, Bu = B;   // operands in the plan's layout
+  if (pl.transpose_a) {
+    Au = at::empty({M, K}, A.options());
+    launch_transpose(p.bf16, A.data_ptr(), Au.data_ptr(), K, M, stream());
   }
-  // eff_layout 2 reaches here only with `direct` (otherwise TN was
-  // re-laid-out to NT above): native-TN split-K, no transposes
-  if (plain && alpha == 1.0 && eff_layout <= 2) {
-    // split-K when the tile grid underfills the chip and K is long
-    int bn_guess = N <= 32 ? 32 : 128;
-    long long tiles = ((long long)(M + 127) / 128) * ((N + bn_guess - 1) / bn_guess);
-    if (tiles < 256 && K >= 1024) {
-      // 8-phase split-K with per-slice slabs + reduce (no fp32 atomics —
-      // the atomic 8-phase variant measured slower, r1 profiles). Covers
-      // the long-K skinny-tile wgrads (BERT dW: 256-divisible M/N).
-      if (eff_layout == 0 && is_bf16(Au) && M % 256 == 0 && N % 256 == 0) {
-        long long t256 = ((long long)M / 256) * (N / 256);
-        int splitk = 1;
-        while ((long long)splitk * 2 * t256 <= 384 && K % (splitk * 2) == 0 &&
-               K / (splitk * 2) >= 256)
-          splitk *= 2;
-        if (splitk > 1 && K % splitk == 0 && (K / splitk) % 32 == 0) {
-          auto slabs = at::empty({(long long)splitk * M * N},
-                                 A.options().dtype(at::kFloat));
-          if (launch_gemm_nt_8ph_splitk(
-                  Au.data_ptr(), Bu.data_ptr(), slabs.data_ptr<float>(),
-                  C.data_ptr(), out_dtype != at::kFloat, M, N, K, splitk, 1,
-                  stream()))
-            return C;
-        }
-      }
+  if (pl.transpose_b) {
+    Bu = at::empty({N, K}, B.options());
+    launch_transpose(p.bf16, B.data_ptr(), Bu.data_ptr(), K, N, stream());
+  }
+  switch (pl.kind) {
+    case GemmKind::G9Slab:
+    case GemmKind::G8Slab:
+      run_slab(pl, Au, Bu, C, M, N, K);
+      return C;
+    case GemmKind::TwoPhaseSplitK: {
       auto C32 = (out_dtype == at::kFloat)
                      ? C.zero_()
                      : at::zeros({M, N}, A.options().dtype(at::kFloat));
-      // (an 8-phase split-K variant with ATOMICS was measured slower here:
-      // the 256^2 tile quadruples each block's fp32 atomic output volume —
-      // see profiles/; the 128^2 2-phase split-K wins for these shapes)
-      launch_gemm_splitk(is_bf16(Au), eff_layout, Au.data_ptr(),
-                         Bu.data_ptr(), C32.data_ptr<float>(), M, N, K,
+      run_splitk(pl, Au, Bu, C32, M, N, K);
+      if (out_dtype != at::kFloat)
+        launch_cast_copy(true, C.data_ptr(), C32.data_ptr<float>(), C.numel(),
                          stream());
-      if (out_dtype == at::kFloat) return C32;
-      launch_cast_copy(true, C.data_ptr(), C32.data_ptr<float>(), C.numel(),
-                       stream());
       return C;
     }
+    default:
+      run_dense(p, pl, Au.data_ptr(), Bu.data_ptr(), C.data_ptr(), bias_ptr);
+      return C;
   }
-  launch_gemm(is_bf16(Au), out_f32, eff_layout, relu, Au.data_ptr(),
-              Bu.data_ptr(), C.data_ptr(), bias_ptr, M, N, K, (float)alpha,
-              (float)beta, stream());
-  return C;
+}
+
+// The plan gemm() (or, with batched, gemm_batched() / bmm_strided()) would
+// execute for a problem, as a plain dict: routing is checkable on a machine
+// with no GPU.
+py::dict gemm_plan(int64_t M, int64_t N, int64_t K, int64_t layout, bool bf16,
+                   bool out_f32, bool has_bias, bool relu, double alpha,
+                   double beta, bool direct, int64_t nbatch, bool strided,
+                   bool batched) {
+  const GemmProblem p{bf16, out_f32, (int)layout, (int)M, (int)N, (int)K,
+                      has_bias, relu, alpha, beta, direct, (int)nbatch,
+                      strided};
+  const GemmPlan pl = batched ? plan_dense(p) : plan_gemm(p);
+  using namespace py::literals;
+  auto to_dict = [](const GemmPlan& q) {
+    return py::dict(
+        "transpose_a"_a = q.transpose_a, "transpose_b"_a = q.transpose_b,
+        "layout"_a = q.layout, "kind"_a = kGemmKindName[(int)q.kind],
+        "tile"_a = py::make_tuple(q.bm, q.bn),
+        "grid"_a = py::make_tuple(q.grid_x, q.grid_y, q.grid_z),
+        "splits"_a = q.splits, "k_chunk"_a = q.k_chunk,
+        "use_swz"_a = q.use_swz, "m_main"_a = q.m_main);
+  };
+  py::dict d = to_dict(pl);
+  if (pl.m_main < p.M)
+    d["remainder"] = to_dict(plan_dense(gemm_remainder(p, pl)));
+  else
+    d["remainder"] = py::none();
+  return d;
 }
 
 // ---- conv ------------------------------------------------------------------
@@ -550,28 +575,20 @@ at::Tensor conv_wgrad(at::Tensor dy, at::Tensor x, int64_t KH, int64_t KW,
     // (P is already transposed for dy) and run the 8-phase split-K slab
     // kernel instead (r2: the rn50 bottleneck 1x1 wgrads were 12% of the
     // step on the 2-phase atomic path).
-    bool done8 = false;
-    if (is_bf16(x) && Cout % 256 == 0 && Cin % 256 == 0 && P % 32 == 0) {
-      long long t256 = ((long long)Cout / 256) * (Cin / 256);
-      int splitk = 1;
-      while ((long long)splitk * 2 * t256 <= 384 && P % (splitk * 2) == 0 &&
-             P / (splitk * 2) >= 256)
-        splitk *= 2;
-      if (splitk > 1 && (P / splitk) % 32 == 0) {
-        auto xt = at::empty({(long long)Cin, P}, x.options());
-        launch_transpose(true, x.data_ptr(), xt.data_ptr(), P, Cin, stream());
-        auto slabs = at::empty({(long long)splitk * Cout * Cin},
-                               x.options().dtype(at::kFloat));
-        done8 = launch_gemm_nt_8ph_splitk(
-            dyt.data_ptr(), xt.data_ptr(), slabs.data_ptr<float>(),
-            dw32.data_ptr(), false, Cout, Cin, (int)P, splitk, 1, stream());
-      }
+    int splits = 1;
+    if (is_bf16(x) && Cout % 256 == 0 && Cin % 256 == 0)
+      splits = slab_splits((long long)(Cout / 256) * (Cin / 256), (int)P);
+    if (splits > 1) {
+      auto xt = at::empty({(long long)Cin, P}, x.options());
+      launch_transpose(true, x.data_ptr(), xt.data_ptr(), P, Cin, stream());
+      run_slab(plan_slab(Cout, Cin, (int)P, splits), dyt, xt, dw32, Cout, Cin,
+               (int)P);
+    } else {
+      run_splitk(plan_splitk(1, Cout, Cin, (int)P), dyt, x, dw32, Cout, Cin,
+                 (int)P);
     }
-    if (!done8)
-      launch_gemm_splitk(is_bf16(x), 1, dyt.data_ptr(), x.data_ptr(),
-                         dw32.data_ptr<float>(), Cout, Cin, (int)P, stream());
   } else {
-    launch_conv_wgrad(is_bf16(x), true, dyt.data_ptr(), x.data_ptr(),
+    launch_conv_wgrad(is_bf16(x), dyt.data_ptr(), x.data_ptr(),
                       dw32.data_ptr(), N, H, W, Cin, Cout, (int)KH, (int)KW,
                       (int)stride, (int)pad, stream());
   }
@@ -609,10 +626,11 @@ at::Tensor bmm_strided(at::Tensor A, at::Tensor B, c10::optional<at::Tensor> C_i
     ldc = N;
   }
   GemmStrides gs{lda, ldb, ldc, (int)heads, saI, sbI, scI};
-  launch_gemm_batched(is_bf16(A), false, (int)layout, false, A.data_ptr(),
-                      B.data_ptr(), C.data_ptr(), nullptr, (int)M, (int)N,
-                      (int)K, (float)alpha, 0.f, (int)nbatch, saO, sbO, scO,
-                      stream(), (int)b_group, gs);
+  const GemmProblem p{is_bf16(A), false, (int)layout, (int)M, (int)N, (int)K,
+                      false, false, alpha, 0.0, true, (int)nbatch,
+                      gs.heads > 1 || gs.lda || gs.ldb || gs.ldc};
+  run_dense(p, plan_dense(p), A.data_ptr(), B.data_ptr(), C.data_ptr(), nullptr,
+            saO, sbO, scO, (int)b_group, gs);
   return C;
 }
 
@@ -639,11 +657,11 @@ at::Tensor gemm_batched(at::Tensor A, at::Tensor B, int64_t layout,
   }
   auto C = at::empty({nb, M, N},
                      A.options().dtype(out_f32 ? at::kFloat : A.scalar_type()));
-  launch_gemm_batched(is_bf16(A), out_f32, (int)layout, false, A.data_ptr(),
-                      B.data_ptr(), C.data_ptr(), nullptr, M, N, K,
-                      (float)alpha, 0.f, nb, (long long)A.size(1) * A.size(2),
-                      (long long)B.size(1) * B.size(2), (long long)M * N,
-                      stream(), (int)b_group);
+  const GemmProblem p{is_bf16(A), out_f32, (int)layout, M, N, K, false, false,
+                      alpha, 0.0, true, nb, false};
+  run_dense(p, plan_dense(p), A.data_ptr(), B.data_ptr(), C.data_ptr(), nullptr,
+            (long long)A.size(1) * A.size(2), (long long)B.size(1) * B.size(2),
+            (long long)M * N, (int)b_group);
   return C;
 }
 
@@ -917,6 +935,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out_f32") = false, py::arg("alpha") = 1.0,
         py::arg("beta") = 0.0, py::arg("C_in") = py::none(),
         py::arg("direct") = false);
+  m.def("gemm_plan", &gemm_plan, py::arg("M"), py::arg("N"), py::arg("K"),
+        py::arg("layout") = 0, py::arg("bf16") = true,
+        py::arg("out_f32") = false, py::arg("has_bias") = false,
+        py::arg("relu") = false, py::arg("alpha") = 1.0, py::arg("beta") = 0.0,
+        py::arg("direct") = false, py::arg("nbatch") = 1,
+        py::arg("strided") = false, py::arg("batched") = false);
   m.def("gemm_batched", &gemm_batched, py::arg("A"), py::arg("B"),
         py::arg("layout"), py::arg("out_f32") = false, py::arg("alpha") = 1.0,
         py::arg("b_group") = 1);

@@ -124,6 +124,23 @@ DEVINL float block_reduce_sum(float v, float* scratch) {
   return total;
 }
 
+// ---- GEMM block id -------------------------------------------------------
+// Linear id of this block in its (x, y) grid; tile_n = id % gridDim.x,
+// tile_m = id / gridDim.x. XCD-aware remap (T1): the dispatcher places
+// block b on XCD b%8, so consecutive ids (which share an operand panel)
+// would land on different per-XCD L2s; give each XCD a contiguous chunk
+// instead (bijective form).
+DEVINL int xcd_block_id(int use_swz) {
+  const int nwg = gridDim.x * gridDim.y;
+  int bid = blockIdx.y * gridDim.x + blockIdx.x;
+  if (use_swz && nwg >= 64) {
+    const int q = nwg >> 3, r = nwg & 7;
+    const int xcd = bid & 7, idx = bid >> 3;
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  return bid;
+}
+
 // ---- canonical K-slice LDS image (shared by gemm.hip / conv.hip) ---------
 // bf16: LINEAR 64-B rows (32 elements) with a 16-B slot XOR swizzle —
 // compatible with global_load_lds (lane-linear dest) and bank-conflict-free

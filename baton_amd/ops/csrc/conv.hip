@@ -925,12 +925,10 @@ void launch_conv_dgrad(bool is_bf16, const void* dy, const void* w, void* dx,
   #undef DG
 }
 
-void launch_conv_wgrad(bool is_bf16, bool out_f32, const void* dy,
-                       const void* x, void* dw, int N, int H, int W, int Cin,
-                       int Cout, int KH, int KW, int stride, int pad,
-                       hipStream_t s) {
+void launch_conv_wgrad(bool is_bf16, const void* dy, const void* x, void* dw,
+                       int N, int H, int W, int Cin, int Cout, int KH, int KW,
+                       int stride, int pad, hipStream_t s) {
   // dw is ALWAYS the fp32 accumulation buffer (bindings allocate zeroed).
-  (void)out_f32;
   ConvShape sh = make_shape(N, H, W, Cin, Cout, KH, KW, stride, pad);
   // tap-replicated kernel for the ResNet hot case (one x/dy HBM pass per
   // (co,ci) tile combo instead of per output column tile — see wt9)

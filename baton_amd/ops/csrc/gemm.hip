@@ -6,7 +6,7 @@
 //   * v_mfma_f32_16x16x32_bf16 (bf16 in, fp32 acc) / v_mfma_f32_16x16x4_f32
 //     (exact f32 — no TF32 on gfx950);
 //   * tile geometry templated: 128x128 (2x2 waves), 128x64 (4x1), 64x128
-//     (1x4) — the launcher picks whichever fills 256 CUs;
+//     (1x4), 128x32 (4x1) — gemm_plan.h picks whichever fills 256 CUs;
 //   * DOUBLE-BUFFERED LDS, one barrier per K-step (2-phase pipeline);
 //   * bf16 staging uses __builtin_amdgcn_global_load_lds (16-B direct
 //     HBM->LDS DMA, no VGPR round-trip) on full interior tiles. glds
@@ -23,11 +23,9 @@
 //   * batched via grid.z (attention: one batch per B*H);
 //   * TN split-K variant for Linear wgrad (small output, long contraction).
 #include "common.h"
-#include <cstdlib>
 
 constexpr int BK = 32;
 constexpr int FRAG = 16;
-constexpr int BM = 128, BN = 128;   // default tile (launcher may narrow)
 
 // LDS layout helpers (lds_off / lds_row_elems) live in common.h.
 
@@ -167,14 +165,12 @@ DEVINL void gemm_mma(const T* a_lds, const T* b_lds, f32x4 (&acc)[MF][NF],
 //   TB=0: B[K,N] row-major; TB=1: B[N,K] row-major.
 
 template <typename T, typename TOUT, bool TA, bool TB, bool RELU,
-          int BM_ = BM, int BN_ = BN, int WAVES_M = 2, int WAVES_N = 2,
-          bool SPLITK = false>
+          int BM_, int BN_, int WAVES_M, int WAVES_N, bool SPLITK>
 __global__ __launch_bounds__(kBlock) void gemm_kernel(
     const T* __restrict__ A, const T* __restrict__ B, TOUT* __restrict__ C,
     const float* __restrict__ bias, int M, int N, int K, float alpha,
     float beta, long long strideA, long long strideB, long long strideC,
-    int k_chunk = 0, int use_swz = 0, int b_group = 1,
-    GemmStrides gs = GemmStrides{0, 0, 0, 1, 0, 0, 0}) {
+    int k_chunk, int use_swz, int b_group, GemmStrides gs) {
   constexpr int WM = BM_ / WAVES_M;
   constexpr int WN = BN_ / WAVES_N;
   constexpr int MF = WM / FRAG;
@@ -201,21 +197,8 @@ __global__ __launch_bounds__(kBlock) void gemm_kernel(
     B += (long long)(blockIdx.z / b_group) * strideB;
     C += (long long)blockIdx.z * strideC;
   }
-  // XCD-aware remap (T1): the dispatcher places block b on XCD b%8, so
-  // consecutive ids (which share an operand panel) would land on different
-  // per-XCD L2s; give each XCD a contiguous chunk instead (bijective form).
-  int tile_n, tile_m2;
-  {
-    const int nwg = gridDim.x * gridDim.y;
-    int bid = blockIdx.y * gridDim.x + blockIdx.x;
-    if (use_swz && nwg >= 64) {
-      const int q = nwg >> 3, r = nwg & 7;
-      const int xcd = bid & 7, idx = bid >> 3;
-      bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    tile_n = bid % gridDim.x;
-    tile_m2 = bid / gridDim.x;
-  }
+  const int bid = xcd_block_id(use_swz);
+  const int tile_n = bid % gridDim.x, tile_m2 = bid / gridDim.x;
   const int m0 = tile_m2 * BM_, n0 = tile_n * BN_;
   const int lane = threadIdx.x & (kWave - 1);
   const int wid = threadIdx.x / kWave;
@@ -299,209 +282,107 @@ __global__ __launch_bounds__(kBlock) void gemm_kernel(
   }
 }
 
-// Instantiations used by bindings.cpp. Layouts: fwd(0,1), dgrad(0,0),
-// wgrad(1,0); each with bf16 and f32 compute; wgrad also with f32 out.
-#define INST_GEMM(T, TOUT, TA, TB, RELU)                                     \
-  template __global__ void gemm_kernel<T, TOUT, TA, TB, RELU, 128, 128, 2, 2>( \
-      const T*, const T*, TOUT*, const float*, int, int, int, float, float,  \
-      long long, long long, long long, int, int, int, GemmStrides);                                 \
-  template __global__ void gemm_kernel<T, TOUT, TA, TB, RELU, 128, 64, 4, 1>( \
-      const T*, const T*, TOUT*, const float*, int, int, int, float, float,  \
-      long long, long long, long long, int, int, int, GemmStrides);                                 \
-  template __global__ void gemm_kernel<T, TOUT, TA, TB, RELU, 64, 128, 1, 4>( \
-      const T*, const T*, TOUT*, const float*, int, int, int, float, float,  \
-      long long, long long, long long, int, int, int, GemmStrides);                                 \
-  template __global__ void gemm_kernel<T, TOUT, TA, TB, RELU, 128, 32, 4, 1>( \
-      const T*, const T*, TOUT*, const float*, int, int, int, float, float,  \
-      long long, long long, long long, int, int, int, GemmStrides);
-
-// split-K variants (fp32 accumulation; layouts NT and NN; all geometries)
-#define INST_GEMM_SPLITK(T, TA, TB)                                          \
-  template __global__ void gemm_kernel<T, float, TA, TB, false, 128, 128, 2, 2, true>( \
-      const T*, const T*, float*, const float*, int, int, int, float, float, \
-      long long, long long, long long, int, int, int, GemmStrides);                                 \
-  template __global__ void gemm_kernel<T, float, TA, TB, false, 128, 64, 4, 1, true>( \
-      const T*, const T*, float*, const float*, int, int, int, float, float, \
-      long long, long long, long long, int, int, int, GemmStrides);                                 \
-  template __global__ void gemm_kernel<T, float, TA, TB, false, 64, 128, 1, 4, true>( \
-      const T*, const T*, float*, const float*, int, int, int, float, float, \
-      long long, long long, long long, int, int, int, GemmStrides);                                 \
-  template __global__ void gemm_kernel<T, float, TA, TB, false, 128, 32, 4, 1, true>( \
-      const T*, const T*, float*, const float*, int, int, int, float, float, \
-      long long, long long, long long, int, int, int, GemmStrides);
-
-INST_GEMM_SPLITK(bf16, false, true)
-INST_GEMM_SPLITK(bf16, false, false)
-INST_GEMM_SPLITK(float, false, true)
-INST_GEMM_SPLITK(float, false, false)
-
-INST_GEMM(bf16, bf16, false, true, false)
-INST_GEMM(bf16, bf16, false, true, true)
-INST_GEMM(bf16, bf16, false, false, false)
-INST_GEMM(bf16, bf16, true, false, false)
-INST_GEMM(bf16, float, true, false, false)
-INST_GEMM(float, float, false, true, false)
-INST_GEMM(float, float, false, true, true)
-INST_GEMM(float, float, false, false, false)
-INST_GEMM(float, float, true, false, false)
-
 // ---- launchers -------------------------------------------------------------
+// Launch exactly the kernel a GemmPlan (gemm_plan.h) names; every routing
+// decision lives in the planner. A false return means the plan does not fit
+// the problem and nothing was launched.
 #include "launchers.h"
 
-void launch_gemm_batched(bool in_bf16, bool out_f32, int layout, bool relu,
-                 const void* A, const void* B, void* C, const float* bias,
-                 int M, int N, int K, float alpha, float beta, int nbatch,
-                 long long strideA, long long strideB, long long strideC,
-                 hipStream_t s, int b_group, GemmStrides gs) {
-  const bool strided = gs.heads > 1 || gs.lda || gs.ldb || gs.ldc;
-  // Tile geometry: prefer 128x128; when that grid underfills the chip
-  // (< ~1.5 blocks/CU), halve the narrower output dim's tile.
-  long long tiles128 = ((long long)(M + 127) / 128) * ((N + 127) / 128) * nbatch;
-  int geom = 0;
-  if (N <= 32) geom = 3;           // 128x32 (4x1 waves) — skinny adapters
-  else if (tiles128 < 384) {
-    if (N <= M) geom = 1;          // 128x64 (4x1 waves)
-    else geom = 2;                 // 64x128 (1x4 waves)
-  }
-  const int bm = geom == 2 ? 64 : 128;
-  const int bn = geom == 1 ? 64 : (geom == 3 ? 32 : 128);
-  dim3 grid((N + bn - 1) / bn, (M + bm - 1) / bm, nbatch);
-  dim3 block(kBlock);
-  // XCD swizzle only when the operands exceed the 256 MiB L3 (T1: costs a
-  // few % when L3-resident, pays ~10% when HBM-bound)
-  const long long op_bytes =
-      ((long long)M * K + (long long)N * K) * (in_bf16 ? 2 : 4) * nbatch;
-  const int use_swz = op_bytes > (200LL << 20) ? 1 : 0;
-  // Deep-pipelined 256x256 8-wave kernel for big bf16 NT tiles (gemm8.hip).
-  // Ragged M (e.g. token counts): run the 256-aligned row block on the
-  // deep kernel and the remainder rows on the 2-phase kernel below.
-  if (in_bf16 && !out_f32 && layout == 0 && !relu && nbatch == 1 &&
-      beta == 0.f && !strided) {   // fp32 bias is fused in the 8-phase epilogue
-    const int m_main = (M / 256) * 256;
-    if (m_main == M) {
-      if (launch_gemm_nt_8ph(A, B, C, bias, M, N, K, alpha, use_swz, s))
-        return;
-    } else if (m_main > 0 && launch_gemm_nt_8ph(A, B, C, bias, m_main, N, K,
-                                                alpha, use_swz, s)) {
-      const bf16* A_rem = (const bf16*)A + (long long)m_main * K;
-      bf16* C_rem = (bf16*)C + (long long)m_main * N;
-      launch_gemm_batched(true, false, 0, false, A_rem, B, C_rem, bias,
-                          M - m_main, N, K, alpha, 0.f, 1, 0, 0, 0, s, 1);
-      return;
-    }
-  }
-  #define GEMM_CALL(T, TOUT, TA, TB, RELU)                                    \
-    do {                                                                      \
-      if (geom == 1)                                                          \
-        hipLaunchKernelGGL((gemm_kernel<T, TOUT, TA, TB, RELU, 128, 64, 4, 1>),\
-                           grid, block, 0, s, (const T*)A, (const T*)B,       \
-                           (TOUT*)C, bias, M, N, K, alpha, beta, strideA,     \
-                           strideB, strideC, 0, use_swz, b_group, gs);         \
-      else if (geom == 2)                                                     \
-        hipLaunchKernelGGL((gemm_kernel<T, TOUT, TA, TB, RELU, 64, 128, 1, 4>),\
-                           grid, block, 0, s, (const T*)A, (const T*)B,       \
-                           (TOUT*)C, bias, M, N, K, alpha, beta, strideA,     \
-                           strideB, strideC, 0, use_swz, b_group, gs);         \
-      else if (geom == 3)                                                     \
-        hipLaunchKernelGGL((gemm_kernel<T, TOUT, TA, TB, RELU, 128, 32, 4, 1>),\
-                           grid, block, 0, s, (const T*)A, (const T*)B,       \
-                           (TOUT*)C, bias, M, N, K, alpha, beta, strideA,     \
-                           strideB, strideC, 0, use_swz, b_group, gs);         \
-      else                                                                    \
-        hipLaunchKernelGGL((gemm_kernel<T, TOUT, TA, TB, RELU, 128, 128, 2, 2>),\
-                           grid, block, 0, s, (const T*)A, (const T*)B,       \
-                           (TOUT*)C, bias, M, N, K, alpha, beta, strideA,     \
-                           strideB, strideC, 0, use_swz, b_group, gs);         \
-    } while (0)
-  if (in_bf16) {
-    if (layout == 0) {          // NT: fwd
-      if (relu) GEMM_CALL(bf16, bf16, false, true, true);
-      else      GEMM_CALL(bf16, bf16, false, true, false);
-    } else if (layout == 1) {   // NN: dgrad
-      GEMM_CALL(bf16, bf16, false, false, false);
-    } else {                    // TN: wgrad
-      if (out_f32) GEMM_CALL(bf16, float, true, false, false);
-      else         GEMM_CALL(bf16, bf16, true, false, false);
-    }
-  } else {
-    if (layout == 0) {
-      if (relu) GEMM_CALL(float, float, false, true, true);
-      else      GEMM_CALL(float, float, false, true, false);
-    } else if (layout == 1) {
-      GEMM_CALL(float, float, false, false, false);
-    } else {
-      GEMM_CALL(float, float, true, false, false);
-    }
-  }
-  #undef GEMM_CALL
+namespace {
+
+template <int BM_, int BN_, int WAVES_M_, int WAVES_N_>
+struct Geom {
+  static constexpr int BM = BM_, BN = BN_, WAVES_M = WAVES_M_, WAVES_N = WAVES_N_;
+};
+
+// The one tile-geometry ladder: the instantiated tiles and their wave grids.
+template <typename F>
+bool with_geom(int bm, int bn, F&& f) {
+  if (bm == 128 && bn == 128) f(Geom<128, 128, 2, 2>{});
+  else if (bm == 128 && bn == 64) f(Geom<128, 64, 4, 1>{});
+  else if (bm == 64 && bn == 128) f(Geom<64, 128, 1, 4>{});
+  else if (bm == 128 && bn == 32) f(Geom<128, 32, 4, 1>{});
+  else return false;
+  return true;
 }
 
-void launch_gemm(bool in_bf16, bool out_f32, int layout, bool relu,
-                 const void* A, const void* B, void* C, const float* bias,
-                 int M, int N, int K, float alpha, float beta, hipStream_t s) {
-  launch_gemm_batched(in_bf16, out_f32, layout, relu, A, B, C, bias, M, N, K,
-                      alpha, beta, 1, 0, 0, 0, s);
+struct GemmArgs {
+  const void *A, *B;
+  void* C;
+  const float* bias;
+  int M, N, K;
+  float alpha, beta;
+  long long strideA, strideB, strideC;
+  int b_group;
+  GemmStrides gs;
+};
+
+template <typename T, typename TOUT, bool TA, bool TB, bool RELU,
+          bool SPLITK = false>
+bool launch_tile(const GemmPlan& pl, const GemmArgs& a, hipStream_t s) {
+  return with_geom(pl.bm, pl.bn, [&](auto g) {
+    using G = decltype(g);
+    hipLaunchKernelGGL(
+        (gemm_kernel<T, TOUT, TA, TB, RELU, G::BM, G::BN, G::WAVES_M,
+                     G::WAVES_N, SPLITK>),
+        dim3(pl.grid_x, pl.grid_y, pl.grid_z), dim3(kBlock), 0, s,
+        (const T*)a.A, (const T*)a.B, (TOUT*)a.C, a.bias, a.M, a.N, a.K,
+        a.alpha, a.beta, a.strideA, a.strideB, a.strideC,
+        SPLITK ? pl.k_chunk : 0, pl.use_swz, a.b_group, a.gs);
+  });
 }
 
-void launch_gemm_splitk(bool in_bf16, int layout, const void* A,
-                        const void* B, float* C, int M, int N, int K,
-                        hipStream_t s) {
-  // layout 0 = NT, 1 = NN. Geometry as the dense launcher, then split K to
-  // fill ~2 blocks/CU.
-  int geom = 0;
-  long long tiles128 = ((long long)(M + 127) / 128) * ((N + 127) / 128);
-  // 128x128 has 2x the arithmetic intensity of the narrow tiles and the
-  // K-split supplies the grid fill, so it wins whenever the chip can be
-  // covered at all (measured +45..100% on the BERT wgrad shapes, BERT
-  // end-to-end +12%); narrow geometries only when even max splits cannot
-  // reach 256 blocks, 128x32 for the skinny-N LoRA shapes.
-  if (N <= 32) geom = 3;
-  else if (tiles128 * ((K + BK - 1) / BK) < 256) geom = (N <= M) ? 1 : 2;
-  // A/B override: BATON_SK_GEOM forces a split-K tile geometry (perf runs)
-  {
-    static int force = [] {
-      const char* e = std::getenv("BATON_SK_GEOM");
-      return e ? std::atoi(e) : -1;
-    }();
-    if (force >= 0 && !(force != 3 && N <= 32)) geom = force;
-  }
-  const int bm = geom == 2 ? 64 : 128;
-  const int bn = geom == 1 ? 64 : (geom == 3 ? 32 : 128);
-  long long tiles = ((long long)(M + bm - 1) / bm) * ((N + bn - 1) / bn);
-  int splits = (int)(512 / (tiles > 0 ? tiles : 1));
-  if (splits < 1) splits = 1;
-  int max_splits = (K + BK - 1) / BK;
-  if (splits > max_splits) splits = max_splits;
-  int k_chunk = ((K + splits - 1) / splits + BK - 1) / BK * BK;
-  splits = (K + k_chunk - 1) / k_chunk;
-  dim3 grid((N + bn - 1) / bn, (M + bm - 1) / bm, splits);
-  #define SK_CALL(T, TA, TB)                                                   \
-    do {                                                                       \
-      if (geom == 1)                                                           \
-        hipLaunchKernelGGL((gemm_kernel<T, float, TA, TB, false, 128, 64, 4, 1, true>), \
-                           grid, dim3(kBlock), 0, s, (const T*)A, (const T*)B, \
-                           C, nullptr, M, N, K, 1.f, 0.f, 0, 0, 0, k_chunk, 0, 1);   \
-      else if (geom == 2)                                                      \
-        hipLaunchKernelGGL((gemm_kernel<T, float, TA, TB, false, 64, 128, 1, 4, true>), \
-                           grid, dim3(kBlock), 0, s, (const T*)A, (const T*)B, \
-                           C, nullptr, M, N, K, 1.f, 0.f, 0, 0, 0, k_chunk, 0, 1);   \
-      else if (geom == 3)                                                      \
-        hipLaunchKernelGGL((gemm_kernel<T, float, TA, TB, false, 128, 32, 4, 1, true>), \
-                           grid, dim3(kBlock), 0, s, (const T*)A, (const T*)B, \
-                           C, nullptr, M, N, K, 1.f, 0.f, 0, 0, 0, k_chunk, 0, 1);   \
-      else                                                                     \
-        hipLaunchKernelGGL((gemm_kernel<T, float, TA, TB, false, 128, 128, 2, 2, true>), \
-                           grid, dim3(kBlock), 0, s, (const T*)A, (const T*)B, \
-                           C, nullptr, M, N, K, 1.f, 0.f, 0, 0, 0, k_chunk, 0, 1);   \
-    } while (0)
-  if (in_bf16) {
-    if (layout == 0) SK_CALL(bf16, false, true);
-    else if (layout == 2) SK_CALL(bf16, true, false);  // native TN (wgrads)
-    else SK_CALL(bf16, false, false);
-  } else {
-    if (layout == 0) SK_CALL(float, false, true);
-    else if (layout == 2) SK_CALL(float, true, false);
-    else SK_CALL(float, false, false);
-  }
-  #undef SK_CALL
+// Layout ladders: NT (fwd), NN (dgrad), TN (wgrad, bf16 also with fp32 out).
+template <typename T>
+bool launch_dense(const GemmPlan& pl, bool out_f32, bool relu,
+                  const GemmArgs& a, hipStream_t s) {
+  if (pl.layout == 0)
+    return relu ? launch_tile<T, T, false, true, true>(pl, a, s)
+                : launch_tile<T, T, false, true, false>(pl, a, s);
+  if (pl.layout == 1) return launch_tile<T, T, false, false, false>(pl, a, s);
+  return out_f32 ? launch_tile<T, float, true, false, false>(pl, a, s)
+                 : launch_tile<T, T, true, false, false>(pl, a, s);
+}
+
+template <typename T>
+bool launch_splitk(const GemmPlan& pl, const GemmArgs& a, hipStream_t s) {
+  if (pl.layout == 0)
+    return launch_tile<T, float, false, true, false, true>(pl, a, s);
+  if (pl.layout == 1)
+    return launch_tile<T, float, false, false, false, true>(pl, a, s);
+  return launch_tile<T, float, true, false, false, true>(pl, a, s);
+}
+
+// the plan's grid must cover the output exactly once
+bool grid_fits(const GemmPlan& pl, int M, int N, int gz) {
+  return pl.bm > 0 && pl.bn > 0 && pl.grid_x == (N + pl.bn - 1) / pl.bn &&
+         pl.grid_y == (M + pl.bm - 1) / pl.bm && pl.grid_z == gz;
+}
+
+}  // namespace
+
+bool launch_gemm_2ph(const GemmPlan& pl, const GemmProblem& p, const void* A,
+                     const void* B, void* C, const float* bias,
+                     long long strideA, long long strideB, long long strideC,
+                     hipStream_t s, int b_group, GemmStrides gs) {
+  if (pl.kind != GemmKind::TwoPhase || !grid_fits(pl, p.M, p.N, p.nbatch))
+    return false;
+  const GemmArgs a{A, B, C, bias, p.M, p.N, p.K, (float)p.alpha, (float)p.beta,
+                   strideA, strideB, strideC, b_group, gs};
+  return p.bf16 ? launch_dense<bf16>(pl, p.out_f32, p.relu, a, s)
+                : launch_dense<float>(pl, p.out_f32, p.relu, a, s);
+}
+
+bool launch_gemm_2ph_splitk(const GemmPlan& pl, bool in_bf16, const void* A,
+                            const void* B, float* C, int M, int N, int K,
+                            hipStream_t s) {
+  // the K slices must tile [0, K) in whole K-steps
+  if (pl.kind != GemmKind::TwoPhaseSplitK || !grid_fits(pl, M, N, pl.splits) ||
+      pl.splits < 1 || pl.k_chunk < BK || pl.k_chunk % BK != 0 ||
+      (long long)pl.splits * pl.k_chunk < K ||
+      (long long)(pl.splits - 1) * pl.k_chunk >= K)
+    return false;
+  const GemmArgs a{A, B, C, nullptr, M, N, K, 1.f, 0.f, 0, 0, 0, 1,
+                   GemmStrides{0, 0, 0, 1, 0, 0, 0}};
+  return in_bf16 ? launch_splitk<bf16>(pl, a, s) : launch_splitk<float>(pl, a, s);
 }

@@ -4,7 +4,13 @@
 // barriers instead of draining at every k-step, which is what caps the
 // simple 2-phase pipeline (~650 TF) well below the chip's reach.
 //
-// Schedule (constructed for this kernel; bf16 NT, full tiles only):
+// Two kernels. g9 (below g8 in this file) is the shipped one: dense with a
+// fused fp32 bias, and split-K into fp32 slabs. It walks 64-wide K-tiles,
+// so a K slice of an odd number of 32-wide k-halves (k_chunk % 64 == 32)
+// cannot run on it; g8, which walks single k-halves, stays as the slab
+// kernel for exactly those slices. gemm_plan.h chooses between them.
+//
+// g8 schedule (constructed for this kernel; bf16 NT, full tiles only):
 //   * K walks in 32-wide "k-halves"; LDS holds FOUR slot-pairs
 //     (A[256][32] + B[256][32] = 32 KiB each, 128 KiB total), rotating
 //     slot = kh & 3;
@@ -28,25 +34,19 @@
 //   * LDS image identical to gemm.hip: linear 64-B rows, 16-B slot XOR
 //     swizzle on the glds SOURCE address and the ds_read offsets.
 //
-// Eligibility (launcher-checked): bf16, NT, M % 256 == 0, N % 256 == 0,
-// K % 64 == 0 (=> rows 16-B aligned), no bias/beta/relu. Everything else
-// takes the 2-phase kernel in gemm.hip.
+// Preconditions (launcher-checked): bf16, NT, M % 256 == 0, N % 256 == 0,
+// K slices of whole k-halves (g8) / K-tiles (g9) (=> rows 16-B aligned),
+// no beta/relu. Everything else takes the 2-phase kernel in gemm.hip.
 #include "common.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace g8 {
 
 constexpr int KH = 32;              // k-half width (one MFMA K)
+static_assert(KH == kBKElems, "slots use the canonical lds_off<bf16> image");
 constexpr int TM = 256, TN = 256;   // C tile
 constexpr int THREADS = 512;        // 8 waves (2 M x 4 N)
 constexpr int SLOT = 256 * KH;      // elements per operand slot
-
-// slot-swizzled element offset within a [256][32] bf16 image (64-B rows)
-DEVINL int soff(int row, int col) {
-  const int sl = col >> 3;
-  return row * KH + ((sl ^ ((row >> 2) & 3)) << 3) + (col & 7);
-}
 
 // stage one operand slot (256 rows x 32 k) via glds; 2 dwordx4 per thread
 DEVINL void stage_slot(bf16* __restrict__ lds, const bf16* __restrict__ src,
@@ -79,33 +79,18 @@ DEVINL void vmwait(int n) {
   }
 }
 
-// SCHED selects the in-loop schedule for A/B experiments (BATON_G8_SCHED):
-//   0 = two phases per k-half, b-frags {2,3} read in phase 1 (r1 shipped)
-//   1 = all 12 fragment reads up front, phase 1 = stage B + MFMA only
-//   2 = fully merged: both stages issued before the wait, one 32-MFMA
-//       cluster per k-half
-template <bool SPLITK, typename TOUT, int SCHED = 0>
+// Split-K slab form: the block at grid.z covers K slice [z * k_chunk,
+// (z + 1) * k_chunk) and writes its fp32 partial tile to slab z of C.
 __global__ __launch_bounds__(THREADS) void gemm_nt_8ph_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
-    TOUT* __restrict__ C, const float* __restrict__ bias, int M, int N, int K,
-    float alpha, int use_swz, int k_chunk) {
+    float* __restrict__ C, int M, int N, int K, int use_swz, int k_chunk) {
   // ONE shared object: 4 slot-pairs [A | B]
   __shared__ bf16 lds[4 * 2 * SLOT];
   auto a_slot = [&](int s) -> bf16* { return lds + s * 2 * SLOT; };
   auto b_slot = [&](int s) -> bf16* { return lds + s * 2 * SLOT + SLOT; };
 
-  int tile_n, tile_m;
-  {
-    const int nwg = gridDim.x * gridDim.y;
-    int bid = blockIdx.y * gridDim.x + blockIdx.x;
-    if (use_swz && nwg >= 64) {
-      const int q = nwg >> 3, r = nwg & 7;
-      const int xcd = bid & 7, idx = bid >> 3;
-      bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    tile_n = bid % gridDim.x;
-    tile_m = bid / gridDim.x;
-  }
+  const int bid = xcd_block_id(use_swz);
+  const int tile_n = bid % gridDim.x, tile_m = bid / gridDim.x;
   const bf16* Atile = A + (long long)tile_m * TM * K;   // lda = K
   const bf16* Btile = B + (long long)tile_n * TN * K;   // ldb = K
   const int m0 = tile_m * TM, n0 = tile_n * TN;
@@ -117,9 +102,8 @@ __global__ __launch_bounds__(THREADS) void gemm_nt_8ph_kernel(
 
   f32x4 acc[8][4] = {};                 // 128 VGPRs of accumulator
 
-  // SPLITK: this block covers K slice [kb, kb + k_chunk)
-  const int kb = SPLITK ? blockIdx.z * k_chunk : 0;
-  const int ke = SPLITK ? min(kb + k_chunk, K) : K;
+  const int kb = blockIdx.z * k_chunk;
+  const int ke = min(kb + k_chunk, K);
   const int nkh = (ke - kb) / KH;
   if (nkh <= 0) return;
   // prologue: stage k-halves 0..2 (or fewer)
@@ -137,19 +121,16 @@ __global__ __launch_bounds__(THREADS) void gemm_nt_8ph_kernel(
     const bf16* As = a_slot(s);
     const bf16* Bs = b_slot(s);
 
-    // ---- phase 0: issue A(kh+3) (and B under SCHED 2), wait, MFMA
+    // ---- phase 0: issue A(kh+3), wait, MFMA nf-pair {0,1}
     if (kh + 3 < nkh) stage_slot(a_slot((kh + 3) & 3), Atile, K, kb + (kh + 3) * KH);
-    if (SCHED == 2 && kh + 3 < nkh)
-      stage_slot(b_slot((kh + 3) & 3), Btile, K, kb + (kh + 3) * KH);
     {
       // outstanding allowed = stages issued after B(kh):
       //   full slot-pairs for kh+1..min(kh+2, nkh-1)  (2 stages each)
-      //   + this phase's A(kh+3) (+B under SCHED 2) if it exists
+      //   + this phase's A(kh+3) if it exists
       int ahead = 0;
       if (kh + 1 <= nkh - 1) ++ahead;
       if (kh + 2 <= nkh - 1) ++ahead;
-      int stages = 2 * ahead +
-                   (kh + 3 <= nkh - 1 ? (SCHED == 2 ? 2 : 1) : 0);
+      int stages = 2 * ahead + (kh + 3 <= nkh - 1 ? 1 : 0);
       vmwait(2 * stages);
     }
     __builtin_amdgcn_s_barrier();       // every wave's slot data visible
@@ -158,43 +139,39 @@ __global__ __launch_bounds__(THREADS) void gemm_nt_8ph_kernel(
 #pragma unroll
     for (int mf = 0; mf < 8; ++mf)
       a_frag[mf] = *reinterpret_cast<const s16x8*>(
-          &As[soff(wm0 + mf * 16 + arow, kfrag)]);
+          &As[lds_off<bf16>(wm0 + mf * 16 + arow, kfrag)]);
 #pragma unroll
-    for (int nf = 0; nf < (SCHED == 0 ? 2 : 4); ++nf)
+    for (int nf = 0; nf < 2; ++nf)
       b_frag[nf] = *reinterpret_cast<const s16x8*>(
-          &Bs[soff(wn0 + nf * 16 + arow, kfrag)]);
+          &Bs[lds_off<bf16>(wn0 + nf * 16 + arow, kfrag)]);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int mf = 0; mf < 8; ++mf)
 #pragma unroll
-      for (int nf = 0; nf < (SCHED == 2 ? 4 : 2); ++nf)
+      for (int nf = 0; nf < 2; ++nf)
         acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             a_frag[mf], b_frag[nf], acc[mf][nf], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
 
-    // ---- phase 1 (SCHED 0/1): issue B(kh+3), MFMA nf-pair {2,3}
-    if (SCHED != 2) {
-      if (kh + 3 < nkh)
-        stage_slot(b_slot((kh + 3) & 3), Btile, K, kb + (kh + 3) * KH);
-      if (SCHED == 0) {
+    // ---- phase 1: issue B(kh+3), MFMA nf-pair {2,3}
+    if (kh + 3 < nkh)
+      stage_slot(b_slot((kh + 3) & 3), Btile, K, kb + (kh + 3) * KH);
 #pragma unroll
-        for (int nf = 2; nf < 4; ++nf)
-          b_frag[nf] = *reinterpret_cast<const s16x8*>(
-              &Bs[soff(wn0 + nf * 16 + arow, kfrag)]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __builtin_amdgcn_s_setprio(1);
+    for (int nf = 2; nf < 4; ++nf)
+      b_frag[nf] = *reinterpret_cast<const s16x8*>(
+          &Bs[lds_off<bf16>(wn0 + nf * 16 + arow, kfrag)]);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int mf = 0; mf < 8; ++mf)
+    for (int mf = 0; mf < 8; ++mf)
 #pragma unroll
-        for (int nf = 2; nf < 4; ++nf)
-          acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a_frag[mf], b_frag[nf], acc[mf][nf], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
+      for (int nf = 2; nf < 4; ++nf)
+        acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            a_frag[mf], b_frag[nf], acc[mf][nf], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_s_barrier();       // slot s free for staging at kh+1
   }
 
@@ -206,23 +183,16 @@ __global__ __launch_bounds__(THREADS) void gemm_nt_8ph_kernel(
 #pragma unroll
   for (int nf = 0; nf < 4; ++nf) {
     const int col = n0 + wn0 + nf * 16 + col_in_frag;
-    // fp32 bias fused into the epilogue (null on the split-K/atomic path —
-    // a per-slice add would apply it gridDim.z times)
-    const float bv = bias ? bias[col] : 0.f;
 #pragma unroll
     for (int mf = 0; mf < 8; ++mf)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = m0 + wm0 + mf * 16 + row_base + r;
-        if (SPLITK)
-          // per-slice slab (plain stores; a tiny reduce kernel sums the
-          // slices) — fp32 atomics at this tile size quadruple the
-          // epilogue's atomic volume and measured slower (r1 profiles)
-          C[(long long)blockIdx.z * M * N + (long long)row * N + col] =
-              (TOUT)(alpha * acc[mf][nf][r]);
-        else
-          C[(long long)row * N + col] =
-              (TOUT)(alpha * acc[mf][nf][r] + bv);
+        // per-slice slab (plain stores; a tiny reduce kernel sums the
+        // slices) — fp32 atomics at this tile size quadruple the
+        // epilogue's atomic volume and measured slower (r1 profiles)
+        C[(long long)blockIdx.z * M * N + (long long)row * N + col] =
+            acc[mf][nf][r];
       }
   }
 }
@@ -284,11 +254,10 @@ DEVINL void stage_half(bf16* __restrict__ lds, const bf16* __restrict__ src,
   }
 }
 
-// NOWAIT: skip the explicit lgkmcnt(0) before each MFMA cluster and let
-// hipcc's own counted lgkm ladders keep the NEXT phase's just-issued
-// reads in flight under the current cluster (the explicit 0-drain
-// serializes them).
-template <bool NOWAIT, bool SPLITK = false, typename TOUT = bf16>
+// No explicit lgkmcnt(0) before the MFMA clusters: hipcc's own counted
+// lgkm ladders keep the NEXT phase's just-issued reads in flight under the
+// current cluster (an explicit 0-drain serializes them).
+template <bool SPLITK = false, typename TOUT = bf16>
 __global__ __launch_bounds__(THREADS) void gemm_nt_g9_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     TOUT* __restrict__ C, const float* __restrict__ bias, int M, int N, int K,
@@ -300,18 +269,8 @@ __global__ __launch_bounds__(THREADS) void gemm_nt_g9_kernel(
     return lds + idx * HALF;
   };
 
-  int tile_n, tile_m;
-  {
-    const int nwg = gridDim.x * gridDim.y;
-    int bid = blockIdx.y * gridDim.x + blockIdx.x;
-    if (use_swz && nwg >= 64) {
-      const int q = nwg >> 3, r = nwg & 7;
-      const int xcd = bid & 7, idx = bid >> 3;
-      bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    tile_n = bid % gridDim.x;
-    tile_m = bid / gridDim.x;
-  }
+  const int bid = xcd_block_id(use_swz);
+  const int tile_n = bid % gridDim.x, tile_m = bid / gridDim.x;
   const bf16* Atile = A + (long long)tile_m * TM * K;
   const bf16* Btile = B + (long long)tile_n * TN * K;
   const int m0 = tile_m * TM, n0 = tile_n * TN;
@@ -424,10 +383,6 @@ __global__ __launch_bounds__(THREADS) void gemm_nt_g9_kernel(
       stage_h(p + 8);
 
       __builtin_amdgcn_s_barrier();
-      if (!NOWAIT) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-      }
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int mf = 0; mf < 4; ++mf)
@@ -513,93 +468,56 @@ __global__ __launch_bounds__(kBlock) void splitk_reduce_kernel(
 
 }  // namespace g8
 
+
+// ---- launchers -------------------------------------------------------------
+// Launch exactly the kernel a GemmPlan (gemm_plan.h) names. The kernels have
+// no bounds handling, so a plan that does not tile the problem exactly is
+// refused (false, nothing launched).
 #include "launchers.h"
 
-bool launch_gemm_nt_8ph(const void* A, const void* B, void* C,
-                        const float* bias, int M, int N, int K, float alpha,
-                        int use_swz, hipStream_t s) {
-  if (M % g8::TM != 0 || N % g8::TN != 0 || K % 64 != 0) return false;
-  // one 8-wave block per CU: the grid must roughly cover the 256 CUs or
-  // the higher-occupancy 2-phase kernel wins (measured: 554 vs 871 TF at
-  // 128 blocks; at 192 blocks the 8-phase already wins — BERT fwd N=768
-  // shapes, r2 A/B +1%); threshold overridable for A/B runs
-  static long long min_blocks = [] {
-    const char* e = std::getenv("BATON_G8_MIN_BLOCKS");
-    return e ? std::atoll(e) : 160LL;
-  }();
-  if ((long long)(M / g8::TM) * (N / g8::TN) < min_blocks) return false;
-  static int sched = [] {
-    const char* e = std::getenv("BATON_G8_SCHED");
-    return e ? std::atoi(e) : 4;  // g9 fine-phase, compiler-counted lgkm (r2 A/B winner)
-  }();
-  dim3 grid(N / g8::TN, M / g8::TM);
-#define G8_CALL(SC)                                                           \
-  hipLaunchKernelGGL((g8::gemm_nt_8ph_kernel<false, bf16, SC>), grid,         \
-                     dim3(g8::THREADS), 0, s, (const bf16*)A, (const bf16*)B, \
-                     (bf16*)C, bias, M, N, K, alpha, use_swz, 0)
-  if (sched == 3 || sched == 4) {
-    if (sched == 4)
-      hipLaunchKernelGGL((g9::gemm_nt_g9_kernel<true>), grid,
-                         dim3(g9::THREADS), 0, s, (const bf16*)A,
-                         (const bf16*)B, (bf16*)C, bias, M, N, K, alpha,
-                         use_swz, 0);
-    else
-      hipLaunchKernelGGL((g9::gemm_nt_g9_kernel<false>), grid,
-                         dim3(g9::THREADS), 0, s, (const bf16*)A,
-                         (const bf16*)B, (bf16*)C, bias, M, N, K, alpha,
-                         use_swz, 0);
-  }
-  else if (sched == 1) G8_CALL(1);
-  else if (sched == 2) G8_CALL(2);
-  else G8_CALL(0);
-#undef G8_CALL
+bool launch_gemm_nt_g9(const GemmPlan& pl, const void* A, const void* B,
+                       void* C, const float* bias, int M, int N, int K,
+                       float alpha, hipStream_t s) {
+  if (pl.kind != GemmKind::G9 || M <= 0 || M % g9::TM != 0 ||
+      N % g9::TN != 0 || K % g9::BK != 0 || pl.grid_x != N / g9::TN ||
+      pl.grid_y != M / g9::TM || pl.grid_z != 1)
+    return false;
+  hipLaunchKernelGGL((g9::gemm_nt_g9_kernel<>), dim3(pl.grid_x, pl.grid_y),
+                     dim3(g9::THREADS), 0, s, (const bf16*)A, (const bf16*)B,
+                     (bf16*)C, bias, M, N, K, alpha, pl.use_swz, 0);
   return true;
 }
 
-// Split-K on the 8-phase kernel: grid.z slices each write a private fp32
+// Split-K on the 8-wave kernels: grid.z slices each write a private fp32
 // slab (plain stores), then splitk_reduce sums them. For the long-K
 // skinny-tile wgrad shapes (BERT dW: 9-36 tiles on 256 CUs) this replaces
-// the 2-phase + fp32-atomic path. Caller picks splitk so that
-// tiles * splitk covers the chip and K/splitk is a multiple of 32.
-bool launch_gemm_nt_8ph_splitk(const void* A, const void* B, float* slabs,
-                               void* out, bool out_bf16, int M, int N, int K,
-                               int splitk, int use_swz, hipStream_t s) {
-  if (M % g8::TM != 0 || N % g8::TN != 0) return false;
-  const int k_chunk = K / splitk;
-  if (k_chunk * splitk != K || k_chunk % 32 != 0 || k_chunk < 64) return false;
-  static int sched9 = [] {
-    const char* e = std::getenv("BATON_G8_SCHED");
-    return e ? std::atoi(e) : 4;
-  }();
-  dim3 grid(N / g8::TN, M / g8::TM, splitk);
-  static int g9wait = [] {
-    const char* e = std::getenv("BATON_G9SPLIT_WAIT");
-    return e ? std::atoi(e) : 0;
-  }();
-  if (sched9 >= 3 && k_chunk % 64 == 0) {
-    if (g9wait)
-      hipLaunchKernelGGL((g9::gemm_nt_g9_kernel<false, true, float>), grid,
-                         dim3(g9::THREADS), 0, s, (const bf16*)A,
-                         (const bf16*)B, slabs, nullptr, M, N, K, 1.0f,
-                         use_swz, k_chunk);
-    else
-      hipLaunchKernelGGL((g9::gemm_nt_g9_kernel<true, true, float>), grid,
-                         dim3(g9::THREADS), 0, s, (const bf16*)A,
-                         (const bf16*)B, slabs, nullptr, M, N, K, 1.0f,
-                         use_swz, k_chunk);
-  }
+// the 2-phase + fp32-atomic path. slabs holds pl.splits * M * N floats.
+bool launch_gemm_nt_slab(const GemmPlan& pl, const void* A, const void* B,
+                         float* slabs, void* out, bool out_bf16, int M, int N,
+                         int K, hipStream_t s) {
+  const bool g9k = pl.kind == GemmKind::G9Slab;
+  if ((!g9k && pl.kind != GemmKind::G8Slab) || M % g8::TM != 0 ||
+      N % g8::TN != 0 || pl.grid_x != N / g8::TN || pl.grid_y != M / g8::TM ||
+      pl.splits < 1 || pl.grid_z != pl.splits ||
+      (long long)pl.k_chunk * pl.splits != K || pl.k_chunk < 64 ||
+      pl.k_chunk % (g9k ? g9::BK : g8::KH) != 0)
+    return false;
+  const dim3 grid(pl.grid_x, pl.grid_y, pl.grid_z);
+  if (g9k)
+    hipLaunchKernelGGL((g9::gemm_nt_g9_kernel<true, float>), grid,
+                       dim3(g9::THREADS), 0, s, (const bf16*)A, (const bf16*)B,
+                       slabs, nullptr, M, N, K, 1.0f, pl.use_swz, pl.k_chunk);
   else
-    hipLaunchKernelGGL((g8::gemm_nt_8ph_kernel<true, float>), grid,
-                       dim3(g8::THREADS), 0, s, (const bf16*)A, (const bf16*)B,
-                       slabs, nullptr, M, N, K, 1.0f, use_swz, k_chunk);
+    hipLaunchKernelGGL(g8::gemm_nt_8ph_kernel, grid, dim3(g8::THREADS), 0, s,
+                       (const bf16*)A, (const bf16*)B, slabs, M, N, K,
+                       pl.use_swz, pl.k_chunk);
   const long long mn = (long long)M * N;
   const int rgrid = elementwise_grid(mn / 4 + 1);
   if (out_bf16)
     hipLaunchKernelGGL(g8::splitk_reduce_kernel<bf16>, dim3(rgrid),
-                       dim3(kBlock), 0, s, slabs, (bf16*)out, mn, splitk);
+                       dim3(kBlock), 0, s, slabs, (bf16*)out, mn, pl.splits);
   else
     hipLaunchKernelGGL(g8::splitk_reduce_kernel<float>, dim3(rgrid),
-                       dim3(kBlock), 0, s, slabs, (float*)out, mn, splitk);
+                       dim3(kBlock), 0, s, slabs, (float*)out, mn, pl.splits);
   return true;
 }
-

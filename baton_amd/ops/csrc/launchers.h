@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gemm_plan.h"
 #include "gemm_strides.h"
 
 // optim.hip
@@ -81,11 +82,6 @@ void launch_gelu_fwd(bool is_bf16, const void* x, void* y, long long n,
 void launch_gelu_bwd(bool is_bf16, const void* dy, const void* x, void* dx,
                      long long n, hipStream_t s);
 
-// gemm.hip — layout: 0 = NT (fwd), 1 = NN (dgrad), 2 = TN (wgrad)
-void launch_gemm(bool in_bf16, bool out_f32, int layout, bool relu,
-                 const void* A, const void* B, void* C, const float* bias,
-                 int M, int N, int K, float alpha, float beta, hipStream_t s);
-
 // conv.hip — NHWC implicit GEMM
 void launch_conv_fwd(bool is_bf16, const void* x, const void* w, void* y,
                      int N, int H, int W, int Cin, int Cout, int KH, int KW,
@@ -93,19 +89,39 @@ void launch_conv_fwd(bool is_bf16, const void* x, const void* w, void* y,
 void launch_conv_dgrad(bool is_bf16, const void* dy, const void* w, void* dx,
                        int N, int H, int W, int Cin, int Cout, int KH, int KW,
                        int stride, int pad, hipStream_t s);
-void launch_conv_wgrad(bool is_bf16, bool out_f32, const void* dy,
-                       const void* x, void* dw, int N, int H, int W, int Cin,
-                       int Cout, int KH, int KW, int stride, int pad,
-                       hipStream_t s);
+void launch_conv_wgrad(bool is_bf16, const void* dy, const void* x, void* dw,
+                       int N, int H, int W, int Cin, int Cout, int KH, int KW,
+                       int stride, int pad, hipStream_t s);
 
-// gemm.hip batched (attention): grid.z = nbatch, per-batch element strides
-void launch_gemm_batched(bool in_bf16, bool out_f32, int layout, bool relu,
-                         const void* A, const void* B, void* C,
-                         const float* bias, int M, int N, int K, float alpha,
-                         float beta, int nbatch, long long strideA,
-                         long long strideB, long long strideC, hipStream_t s,
-                         int b_group = 1,
-                         GemmStrides gs = GemmStrides{0, 0, 0, 1, 0, 0, 0});
+// GEMM launchers (gemm.hip, gemm8.hip): each launches exactly the kernel,
+// tile, grid and K split the GemmPlan names (gemm_plan.h decides) and
+// returns false, launching nothing, when the plan does not fit the problem.
+// Layout comes from the plan: 0 = NT (fwd), 1 = NN (dgrad), 2 = TN (wgrad).
+
+// gemm.hip — 2-phase kernel, dense; batched via grid.z = nbatch with
+// per-batch element strides (attention)
+bool launch_gemm_2ph(const GemmPlan& pl, const GemmProblem& p, const void* A,
+                     const void* B, void* C, const float* bias,
+                     long long strideA, long long strideB, long long strideC,
+                     hipStream_t s, int b_group = 1,
+                     GemmStrides gs = GemmStrides{0, 0, 0, 1, 0, 0, 0});
+
+// gemm.hip — 2-phase split-K: fp32 atomic accumulation over K slices into
+// a zeroed C
+bool launch_gemm_2ph_splitk(const GemmPlan& pl, bool in_bf16, const void* A,
+                            const void* B, float* C, int M, int N, int K,
+                            hipStream_t s);
+
+// gemm8.hip — deep-pipelined 256x256 8-wave NT kernel (bf16 full tiles),
+// fused fp32 bias
+bool launch_gemm_nt_g9(const GemmPlan& pl, const void* A, const void* B,
+                       void* C, const float* bias, int M, int N, int K,
+                       float alpha, hipStream_t s);
+
+// gemm8.hip — 8-wave split-K: per-slice fp32 slabs + reduce (no atomics)
+bool launch_gemm_nt_slab(const GemmPlan& pl, const void* A, const void* B,
+                         float* slabs, void* out, bool out_bf16, int M, int N,
+                         int K, hipStream_t s);
 
 // attention.hip — row softmax with scale + optional causal mask
 void launch_softmax_fwd(bool is_bf16, const void* x, void* y, long long R,
@@ -129,11 +145,6 @@ void launch_silu_mul_bwd(bool is_bf16, const void* dy, const void* a,
                          const void* b, void* da, void* db, long long n,
                          hipStream_t s);
 
-// gemm.hip split-K (layouts NT/NN): fp32 atomic accumulation over K slices
-void launch_gemm_splitk(bool in_bf16, int layout, const void* A,
-                        const void* B, float* C, int M, int N, int K,
-                        hipStream_t s);
-
 // fedmath.hip — LDS-tiled matrix transpose [R,C] -> [C,R]
 void launch_transpose(bool is_bf16, const void* in, void* out, int R, int C,
                       hipStream_t s);
@@ -141,17 +152,6 @@ void launch_transpose(bool is_bf16, const void* in, void* out, int R, int C,
 // fedmath.hip — column sum (bias gradients): out[c] = sum_r x[r,c], fp32
 void launch_colsum(bool is_bf16, const void* x, float* out, long long R, int C,
                    hipStream_t s);
-
-// gemm8.hip — deep-pipelined 256x256 8-wave NT kernel (bf16 full tiles);
-// returns false when the shape is ineligible (caller falls back)
-bool launch_gemm_nt_8ph(const void* A, const void* B, void* C,
-                        const float* bias, int M, int N, int K, float alpha,
-                        int use_swz, hipStream_t s);
-
-// gemm8.hip — split-K 8-phase: per-slice fp32 slabs + reduce (no atomics)
-bool launch_gemm_nt_8ph_splitk(const void* A, const void* B, float* slabs,
-                               void* out, bool out_bf16, int M, int N, int K,
-                               int splitk, int use_swz, hipStream_t s);
 
 // flash.hip — fused flash attention (bf16, DH in {32,64,128}); strides in
 // elements as [batch, seq, head] triples; returns false if DH unsupported

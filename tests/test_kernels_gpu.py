@@ -690,6 +690,14 @@ def test_gemm_router_paths(M, N, K, layout):
         A = torch.randn(K, M, device=DEV).to(dt).contiguous()
         B = torch.randn(K, N, device=DEV).to(dt).contiguous()
         ref = A.float().t() @ B.float()
+    want = {
+        (2048, 16, 4096, 0): "TwoPhaseSplitK",
+        (2048, 16, 4096, 1): "TwoPhaseSplitK",
+        (768, 768, 4096, 2): "G9Slab",
+        (512, 30522, 768, 0): "TwoPhase",
+        (4096, 768, 30522, 1): "TwoPhaseSplitK",
+    }[(M, N, K, layout)]
+    assert OPS.gemm_plan(M, N, K, layout=layout)["kind"] == want
     C = OPS.gemm(A, B, layout)
     assert_close(C, ref, 0.05, 0.06 * K**0.5, f"router M{M} N{N} K{K} l{layout}")
 
@@ -721,9 +729,13 @@ def test_colsum_kernel():
 
 
 def test_gemm_nt_8phase_path():
-    """The 256x256 deep-pipelined NT kernel (full-tile bf16 shapes) vs
-    torch fp32 — exercises the counted-vmcnt glds schedule."""
-    for M, N, K in [(256, 256, 64), (512, 768, 128), (1024, 512, 4096)]:
+    """Full-256-tile bf16 NT shapes vs torch fp32. The two small ones sit
+    far below the 160-block gate of the deep-pipelined kernel and run the
+    2-phase kernel; the long-K one takes the g9 split-K slab route."""
+    for (M, N, K), kind in [((256, 256, 64), "TwoPhase"),
+                            ((512, 768, 128), "TwoPhase"),
+                            ((1024, 512, 4096), "G9Slab")]:
+        assert OPS.gemm_plan(M, N, K)["kind"] == kind
         torch.manual_seed(50 + K)
         A = torch.randn(M, K, device=DEV, dtype=torch.bfloat16).contiguous()
         B = torch.randn(N, K, device=DEV, dtype=torch.bfloat16).contiguous()
@@ -740,6 +752,7 @@ def test_gemm_nt_8phase_large_grid():
     torch.manual_seed(51)
     M, N = 4096, 2560                # (4096/256)*(2560/256) = 160 blocks
     for K in (512, 448):             # 448 = 7 K-tiles: odd B-parity tail
+        assert OPS.gemm_plan(M, N, K)["kind"] == "G9"
         A = torch.randn(M, K, device=DEV, dtype=torch.bfloat16).contiguous()
         B = torch.randn(N, K, device=DEV, dtype=torch.bfloat16).contiguous()
         C = OPS.gemm(A, B, 0)
@@ -778,15 +791,42 @@ def test_resnet_eval_mode_gpu():
 
 
 def test_gemm_nt_8phase_ragged_m():
-    """Ragged token counts (M % 256 != 0) split: 8-phase main block +
-    2-phase remainder rows (the Llama lm_head shape class)."""
+    """Ragged token count (M % 256 != 0) with a small tile grid and long
+    K: 16 x 4 tiles < 256, so this is the 2-phase atomic split-K (ragged M
+    rules out the slab route). The G9 main block + remainder split is
+    covered by test_gemm_nt_uncovered_routes."""
     torch.manual_seed(70)
     M, N, K = 2048 - 48, 512, 1024   # M = 2000: 7 full 256-tiles + 208 rows
+    assert OPS.gemm_plan(M, N, K)["kind"] == "TwoPhaseSplitK"
     A = torch.randn(M, K, device=DEV, dtype=torch.bfloat16).contiguous()
     B = torch.randn(N, K, device=DEV, dtype=torch.bfloat16).contiguous()
     C = OPS.gemm(A, B, 0)
     ref = A.float() @ B.float().t()
     assert_close(C, ref, 0.05, 0.05 * K**0.5, "8ph ragged M")
+
+
+@pytest.mark.parametrize(
+    "M,N,K,kind",
+    [
+        (256, 256, 1152, "G8Slab"),   # k_chunk 288 = 9 k-halves: not g9's
+        (256, 256, 1280, "G9Slab"),   # k_chunk 320 = 5 K-tiles: odd tail
+        (2608, 4096, 192, "G9"),      # 2560 rows G9 + 48 rows 2-phase
+    ],
+)
+def test_gemm_nt_uncovered_routes(M, N, K, kind):
+    """The smallest shapes that reach the g8 slab kernel, the g9 slab
+    odd-K-tile tail, and the ragged-M G9 main block + 2-phase remainder."""
+    plan = OPS.gemm_plan(M, N, K)
+    assert plan["kind"] == kind
+    if M % 256:
+        assert plan["m_main"] == M // 256 * 256
+        assert plan["remainder"]["kind"] == "TwoPhase"
+    torch.manual_seed(72)
+    A = torch.randn(M, K, device=DEV, dtype=torch.bfloat16).contiguous()
+    B = torch.randn(N, K, device=DEV, dtype=torch.bfloat16).contiguous()
+    C = OPS.gemm(A, B, 0)
+    ref = A.float() @ B.float().t()
+    assert_close(C, ref, 0.05, 0.05 * K**0.5, f"{kind} {M}x{N}x{K}")
 
 
 def test_linear_frozen_weight_t_path():
@@ -991,6 +1031,7 @@ def test_gemm_tn_splitk_slab_vs_torch(M, N, K):
     torch.manual_seed(17)
     A = (torch.randn(K, M, device=DEV) * 0.3).bfloat16()   # dy [K=BS, M=outf]
     B = (torch.randn(K, N, device=DEV) * 0.3).bfloat16()   # x  [K=BS, N=inf]
+    assert OPS.gemm_plan(M, N, K, layout=2)["kind"] == "G9Slab"
     C = OPS.gemm(A, B, 2)                                   # TN: A^T @ B
     ref = A.float().t() @ B.float()
     assert_close(C, ref, 0.02, 0.5, f"tn splitk {M}x{N}x{K}")
@@ -1034,13 +1075,15 @@ def test_conv_wgrad_1x1_slab_splitk_vs_torch():
     N, H, W, Cin, Cout = 64, 16, 16, 256, 512
     x = (torch.randn(N, H, W, Cin, device=DEV) * 0.5).bfloat16()
     dy = (torch.randn(N, H, W, Cout, device=DEV) * 0.1).bfloat16()
+    npix = N * H * W
+    # the wgrad is the NT problem dy_t[Cout, P] @ x_t[Cin, P]^T
+    assert OPS.gemm_plan(Cout, Cin, npix)["kind"] == "G9Slab"
     dw = OPS.conv_wgrad(dy, x, 1, 1, 1, 0, True)
     xn = x.float().permute(0, 3, 1, 2)
     dyn = dy.float().permute(0, 3, 1, 2)
     ref = torch.nn.grad.conv2d_weight(xn, (Cout, Cin, 1, 1), dyn, stride=1,
                                       padding=0)
     ref = ref.permute(0, 2, 3, 1).contiguous()
-    npix = N * H * W
     assert_close(dw, ref, 0.05, 0.06 * npix**0.5, "1x1 slab wgrad")
 
 

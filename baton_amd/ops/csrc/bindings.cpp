@@ -9,6 +9,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "launchers.h"
+#include "wgrad_px_map.h"
 
 namespace {
 
@@ -560,43 +561,125 @@ at::Tensor conv_wgrad(at::Tensor dy, at::Tensor x, int64_t KH, int64_t KW,
   int N = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3);
   int Cout = dy.size(3);
   // split-K accumulates in fp32 (zero-init); cast down only if requested.
-  // dy transposed once ([P,Cout] -> [Cout,P]) so the wgrad A operand
-  // stages direct/glds (k = pixel contiguous).
   long long P = (long long)dy.size(0) * dy.size(1) * dy.size(2);
-  auto dyt = at::empty({(long long)Cout, P}, dy.options());
-  launch_transpose(is_bf16(dy), dy.data_ptr(), dyt.data_ptr(), P, Cout,
-                   stream());
   auto dw32 = at::zeros({Cout, KH, KW, Cin}, x.options().dtype(at::kFloat));
-  if (KH == 1 && KW == 1 && stride == 1 && pad == 0) {
-    // 1x1 stride-1 wgrad IS a dense GEMM: dw[Cout,Cin] = dy_t[Cout,P] @
-    // x[P,Cin], NN, K = pixels — the split-K GEMM runs it at GEMM speed
-    // (the conv-path x gather measured ~68 TF on these shapes, the NN
-    // split-K ~250 TF). When Cout/Cin are 256-divisible, transpose x once
-    // (P is already transposed for dy) and run the 8-phase split-K slab
-    // kernel instead (r2: the rn50 bottleneck 1x1 wgrads were 12% of the
-    // step on the 2-phase atomic path).
-    int splits = 1;
-    if (is_bf16(x) && Cout % 256 == 0 && Cin % 256 == 0)
-      splits = slab_splits((long long)(Cout / 256) * (Cin / 256), (int)P);
-    if (splits > 1) {
-      auto xt = at::empty({(long long)Cin, P}, x.options());
-      launch_transpose(true, x.data_ptr(), xt.data_ptr(), P, Cin, stream());
-      run_slab(plan_slab(Cout, Cin, (int)P, splits), dyt, xt, dw32, Cout, Cin,
-               (int)P);
-    } else {
-      run_splitk(plan_splitk(1, Cout, Cin, (int)P), dyt, x, dw32, Cout, Cin,
-                 (int)P);
-    }
+  // 3x3 stride-1: the pixel-major kernel reads dy as it is
+  if (launch_conv_wgrad_px(is_bf16(x), dy.data_ptr(), x.data_ptr(),
+                           dw32.data_ptr(), N, H, W, Cin, Cout, (int)KH,
+                           (int)KW, (int)stride, (int)pad, stream())) {
+    // done
   } else {
-    launch_conv_wgrad(is_bf16(x), dyt.data_ptr(), x.data_ptr(),
-                      dw32.data_ptr(), N, H, W, Cin, Cout, (int)KH, (int)KW,
-                      (int)stride, (int)pad, stream());
+    // every other route wants dy transposed once ([P,Cout] -> [Cout,P]) so
+    // the wgrad A operand stages direct/glds (k = pixel contiguous)
+    auto dyt = at::empty({(long long)Cout, P}, dy.options());
+    launch_transpose(is_bf16(dy), dy.data_ptr(), dyt.data_ptr(), P, Cout,
+                     stream());
+    if (KH == 1 && KW == 1 && stride == 1 && pad == 0) {
+      // 1x1 stride-1 wgrad IS a dense GEMM: dw[Cout,Cin] = dy_t[Cout,P] @
+      // x[P,Cin], NN, K = pixels — the split-K GEMM runs it at GEMM speed
+      // (the conv-path x gather measured ~68 TF on these shapes, the NN
+      // split-K ~250 TF). When Cout/Cin are 256-divisible, transpose x once
+      // (P is already transposed for dy) and run the 8-phase split-K slab
+      // kernel instead (r2: the rn50 bottleneck 1x1 wgrads were 12% of the
+      // step on the 2-phase atomic path).
+      int splits = 1;
+      if (is_bf16(x) && Cout % 256 == 0 && Cin % 256 == 0)
+        splits = slab_splits((long long)(Cout / 256) * (Cin / 256), (int)P);
+      if (splits > 1) {
+        auto xt = at::empty({(long long)Cin, P}, x.options());
+        launch_transpose(true, x.data_ptr(), xt.data_ptr(), P, Cin, stream());
+        run_slab(plan_slab(Cout, Cin, (int)P, splits), dyt, xt, dw32, Cout,
+                 Cin, (int)P);
+      } else {
+        run_splitk(plan_splitk(1, Cout, Cin, (int)P), dyt, x, dw32, Cout, Cin,
+                   (int)P);
+      }
+    } else {
+      launch_conv_wgrad(is_bf16(x), dyt.data_ptr(), x.data_ptr(),
+                        dw32.data_ptr(), N, H, W, Cin, Cout, (int)KH, (int)KW,
+                        (int)stride, (int)pad, stream());
+    }
   }
   if (out_f32 || x.scalar_type() == at::kFloat) return dw32;
   auto dw = at::empty({Cout, KH, KW, Cin}, x.options());
   launch_cast_copy(true, dw.data_ptr(), dw32.data_ptr<float>(), dw.numel(),
                    stream());
   return dw;
+}
+
+
+// The index maps of the pixel-major 3x3 wgrad (wgrad_px_map.h) for one
+// k-step, as plain lists: checkable on a machine with no GPU. The kernel
+// calls the same functions.
+py::dict wgrad_px_map(int64_t N, int64_t H, int64_t W, int64_t step) {
+  using namespace py::literals;
+  TORCH_CHECK(wgpx::eligible(true, (int)N, (int)H, (int)W, 64, 64, 3, 3, 1, 1),
+              "wgrad_px_map: shape not eligible");
+  const wgpx::Geom g = wgpx::make_geom((int)H, (int)W);
+  const long long p0 = step * wgpx::PXK;
+  TORCH_CHECK(step >= 0 && p0 < N * H * W, "wgrad_px_map: step out of range");
+  const int h0 = (int)((p0 / W) % H);
+  const int passes = wgpx::passes_of((int)W);
+  // staging: chunk c = pass * THREADS + thread -> byte 16 c of the buffer
+  py::list stage, window, dy_rows;
+  for (int i = 0; i < wgpx::PXK; ++i) dy_rows.append(py::none());
+  for (int i = 0; i < g.slots; ++i) window.append(py::none());
+  for (int c = 0; c < passes * wgpx::THREADS; ++c) {
+    const wgpx::ChunkSrc cs = wgpx::chunk_src(g, c);
+    const bool ok = cs.kind == 1 ||
+                    (cs.kind == 2 && wgpx::x_row_valid(g, h0, cs.hrel));
+    const long long px = ok ? p0 + cs.rel : -1;   // flat source pixel
+    stage.append(py::make_tuple(c / wgpx::THREADS, c % wgpx::THREADS, 16 * c,
+                                ok ? cs.kind : 0, px, cs.sub));
+    const int row = c / wgpx::CPR;
+    if (c % wgpx::CPR == 0 && row < wgpx::PXK) dy_rows[row] = cs.rel;
+    if (c % wgpx::CPR == 0 && row >= wgpx::PXK && row < wgpx::PXK + g.slots &&
+        ok)
+      window[row - wgpx::PXK] = py::make_tuple(
+          px / (H * W), (px / W) % H, px % W);
+  }
+  py::list kpix, a_addr, b_addr;
+  for (int k = 0; k < wgpx::PXK; ++k)
+    kpix.append(wgpx::lin_pixel((int)W, wgpx::kslot_lin(k)));
+  for (int r = 0; r < 2; ++r) {
+    py::list la;
+    for (int l = 0; l < 64; ++l) la.append(wgpx::a_read_addr(l, r));
+    a_addr.append(la);
+  }
+  for (int t = 0; t < 9; ++t) {
+    py::list lt;
+    for (int r = 0; r < 2; ++r) {
+      py::list lb;
+      for (int l = 0; l < 64; ++l)
+        lb.append(wgpx::b_read_addr(g, l, r) +
+                  wgpx::tap_off(g, t / 3, t % 3) * wgpx::ROWB);
+      lt.append(lb);
+    }
+    b_addr.append(lt);
+  }
+  return py::dict(
+      "row_bytes"_a = wgpx::ROWB, "dy_rows_base"_a = 0,
+      "window_base"_a = wgpx::PXK * wgpx::ROWB, "pitch"_a = g.pitch,
+      "window_rows"_a = g.wrows, "slots"_a = g.slots, "passes"_a = passes,
+      "threads"_a = wgpx::THREADS, "buffer_bytes"_a = passes * wgpx::THREADS * 16,
+      "claimed_conflict_degree"_a = 1, "stage"_a = stage, "window"_a = window,
+      "dy_rows"_a = dy_rows, "kslot_pixel"_a = kpix, "a_addr"_a = a_addr,
+      "b_addr"_a = b_addr);
+}
+
+bool wgrad_px_eligible(bool bf16, int64_t N, int64_t H, int64_t W, int64_t Cin,
+                       int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
+                       int64_t pad) {
+  return wgpx::eligible(bf16, (int)N, (int)H, (int)W, (int)Cin, (int)Cout,
+                        (int)KH, (int)KW, (int)stride, (int)pad);
+}
+
+py::tuple wgrad_px_split(int64_t N, int64_t H, int64_t W, int64_t Cin,
+                         int64_t Cout) {
+  const long long steps = N * H * W / wgpx::PXK;
+  const int sps = wgpx::steps_per_split(
+      steps, (int)(Cin / wgpx::TILE) * (int)(Cout / wgpx::TILE));
+  return py::make_tuple(steps, sps, (steps + sps - 1) / sps);
 }
 
 
@@ -956,4 +1039,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_fwd", &conv_fwd);
   m.def("conv_dgrad", &conv_dgrad);
   m.def("conv_wgrad", &conv_wgrad);
+  m.def("wgrad_px_map", &wgrad_px_map, py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("step"));
+  m.def("wgrad_px_eligible", &wgrad_px_eligible);
+  m.def("wgrad_px_split", &wgrad_px_split);
 }

@@ -89,6 +89,7 @@ void launch_conv_fwd(bool is_bf16, const void* x, const void* w, void* y,
 void launch_conv_dgrad(bool is_bf16, const void* dy, const void* w, void* dx,
                        int N, int H, int W, int Cin, int Cout, int KH, int KW,
                        int stride, int pad, hipStream_t s);
+// dy here is the TRANSPOSED [Cout][P] copy
 void launch_conv_wgrad(bool is_bf16, const void* dy, const void* x, void* dw,
                        int N, int H, int W, int Cin, int Cout, int KH, int KW,
                        int stride, int pad, hipStream_t s);
@@ -196,3 +197,10 @@ bool launch_conv_halo_fwd(const void* x, const void* w, void* y, int N, int H,
                           int W, int Cin, int Cout, hipStream_t s);
 bool launch_conv_halo_dgrad(const void* dy, const void* w_t, void* dx, int N,
                             int H, int W, int Cin, int Cout, hipStream_t s);
+
+// conv_wgrad_px.hip — pixel-major tap-shared 3x3 stride-1 wgrad: dy in its
+// natural [P][Cout] layout, dw the zeroed fp32 buffer; false (nothing
+// launched) when wgpx::eligible() (wgrad_px_map.h) rejects the problem
+bool launch_conv_wgrad_px(bool is_bf16, const void* dy, const void* x,
+                          void* dw, int N, int H, int W, int Cin, int Cout,
+                          int KH, int KW, int stride, int pad, hipStream_t s);

@@ -31,6 +31,7 @@ SRC = [
         "conv.hip",
         "conv8.hip",
         "conv_halo.hip",
+        "conv_wgrad_px.hip",
     ]
 ]
 

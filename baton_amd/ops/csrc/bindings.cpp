@@ -10,6 +10,7 @@
 
 #include "launchers.h"
 #include "wgrad_px_map.h"
+#include "dgrad_phase_map.h"
 
 namespace {
 
@@ -683,6 +684,49 @@ py::tuple wgrad_px_split(int64_t N, int64_t H, int64_t W, int64_t Cin,
 }
 
 
+// The phase map of the stride-2 dgrad (dgrad_phase_map.h) as plain lists:
+// checkable on a machine with no GPU. The kernel calls the same functions.
+// "classes" is in grid order; "rows" gives each class row's (n, h, w),
+// "blocks" each block's (class, M tile within the class, N tile) for a
+// grid of n_tiles N tiles, with or without the XCD remap.
+py::dict dgrad_phase_map(int64_t N, int64_t H, int64_t W, int64_t KH,
+                         int64_t KW, int64_t stride, int64_t pad, int64_t BM,
+                         int64_t n_tiles, bool swz) {
+  using namespace py::literals;
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && BM > 0 && n_tiles > 0 &&
+                  dgph::eligible((int)N, (int)H, (int)W, 32, (int)KH, (int)KW,
+                                 (int)stride, (int)pad, 32),
+              "dgrad_phase_map: shape not eligible");
+  const dgph::Map m = dgph::make_map((int)N, (int)H, (int)W, (int)KH, (int)KW,
+                                     (int)pad, (int)BM);
+  py::list classes;
+  for (int i = 0; i < dgph::NCLS; ++i) {
+    const dgph::Class& c = m.cls[i];
+    py::list taps, rows;
+    for (int t = c.tap0; t < c.tap0 + c.ntaps; ++t)
+      taps.append(py::make_tuple((int)m.taps[t].kh, (int)m.taps[t].kw,
+                                 (int)m.taps[t].dh, (int)m.taps[t].dw));
+    for (int r = 0; r < c.rows; ++r) {
+      const dgph::RowPos p = dgph::row_pos(c, r);
+      const int px = dgph::row_pixel(m, c, r);
+      TORCH_CHECK(px == (p.n * (int)H + 2 * p.a + c.ph) * (int)W + 2 * p.b + c.pw);
+      rows.append(py::make_tuple(px / (int)(H * W), (px / (int)W) % (int)H,
+                                 px % (int)W));
+    }
+    classes.append(py::dict("ph"_a = c.ph, "pw"_a = c.pw, "Hc"_a = c.Hc,
+                            "Wc"_a = c.Wc, "rows"_a = rows, "n_rows"_a = c.rows,
+                            "tile0"_a = c.tile0, "tiles"_a = c.tiles,
+                            "taps"_a = taps));
+  }
+  py::list blocks;
+  for (int b = 0; b < m.m_tiles * (int)n_tiles; ++b) {
+    const dgph::Tile t = dgph::block_tile(m, b, (int)n_tiles, swz ? 1 : 0);
+    blocks.append(py::make_tuple(t.cls, t.m_tile, t.n_tile));
+  }
+  return py::dict("BM"_a = m.BM, "m_tiles"_a = m.m_tiles, "classes"_a = classes,
+                  "blocks"_a = blocks);
+}
+
 // Strided batched GEMM over tensor VIEWS: operands may be non-contiguous
 // slices of [B, S, h, dh] / [B, S, 3, h, dh] tensors (the attention path
 // consumes them in place — no permute copies). Layouts as gemm(); all
@@ -1039,6 +1083,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_fwd", &conv_fwd);
   m.def("conv_dgrad", &conv_dgrad);
   m.def("conv_wgrad", &conv_wgrad);
+  m.def("dgrad_phase_map", &dgrad_phase_map, py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("KH"), py::arg("KW"), py::arg("stride"),
+        py::arg("pad"), py::arg("BM"), py::arg("n_tiles") = 1,
+        py::arg("swz") = false);
   m.def("wgrad_px_map", &wgrad_px_map, py::arg("N"), py::arg("H"),
         py::arg("W"), py::arg("step"));
   m.def("wgrad_px_eligible", &wgrad_px_eligible);

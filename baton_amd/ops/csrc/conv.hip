@@ -15,9 +15,12 @@
 //     (ci,kw,kh / co,kw,kh) advances INCREMENTALLY by CBK per staged tile
 //     — the hot loop has no integer division at all on the fast path
 //     (channels % 32 == 0, i.e. every ResNet layer but the stem);
+//   * stride-2 dgrad is PHASE-DECOMPOSED (dgrad_phase_map.h): M tiles per
+//     input-parity class, K loop over that class's live taps only;
 //   * wgrad splits the pixel contraction over grid.z (fp32 atomics);
 //   * LDS rows padded +8 elements: conflict-free ds_read_b128 groups.
 #include "common.h"
+#include "dgrad_phase_map.h"
 
 constexpr int CBK = 32;
 constexpr int CFRAG = 16;
@@ -267,6 +270,49 @@ struct DgradAStager {
       }
     } else {
       k_generic += CBK;
+    }
+  }
+};
+
+// Stride-2 dgrad A, one phase class (dgrad_phase_map.h): rows = the class's
+// input pixels (n, a, b), k = (the class's taps, co). A tap reads
+// dy[n, a + dh, b + dw]: no stride test, only the ho / wo bounds. The tap
+// walk itself is block-uniform and lives in the kernel.
+template <typename T, int ROWS>
+struct DgradPhaseAStager {
+  static constexpr int ELEMS = 16 / (int)sizeof(T);
+  static constexpr int TPR = CBK / ELEMS;
+  static constexpr int RPP = kBlock / TPR;
+  static constexpr int PASSES = ROWS / RPP;
+  int kc;
+  int n[PASSES], a[PASSES], b[PASSES];
+  bool ok[PASSES];
+
+  DEVINL void init(const dgph::Class& c, int r0) {
+    kc = (threadIdx.x % TPR) * ELEMS;
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+      const int r = r0 + p * RPP + threadIdx.x / TPR;
+      const dgph::RowPos pos = dgph::row_pos(c, r);
+      n[p] = pos.n; a[p] = pos.a; b[p] = pos.b;
+      ok[p] = r < c.rows;
+    }
+  }
+
+  DEVINL void stage(T* __restrict__ lds, const T* __restrict__ dy,
+                    const ConvShape& sh, int dh, int dw, int co0) {
+    using VT = typename VecTraits<T>::VecT;
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+      VT v;
+      T* vp = reinterpret_cast<T*>(&v);
+#pragma unroll
+      for (int j = 0; j < ELEMS; ++j) vp[j] = (T)0.f;
+      const int ho = a[p] + dh, wo = b[p] + dw;
+      if (ok[p] && ho >= 0 && ho < sh.HO && wo >= 0 && wo < sh.WO)
+        v = *reinterpret_cast<const VT*>(
+            &dy[(((long long)n[p] * sh.HO + ho) * sh.WO + wo) * sh.Cout + co0 + kc]);
+      *reinterpret_cast<VT*>(&lds[lds_off<T>(p * RPP + threadIdx.x / TPR, kc)]) = v;
     }
   }
 };
@@ -523,6 +569,71 @@ __global__ __launch_bounds__(kBlock) void conv_dgrad_kernel(
       }
 }
 
+// Stride-2 dgrad, phase-decomposed (dgrad_phase_map.h): an M tile holds
+// input pixels of ONE parity class and the K loop walks only that class's
+// taps x Cout — the k-steps the kernel above would stage as zero rows are
+// never issued. The remaining k-steps are the same ones in the same order,
+// so the result is bit-identical. Needs Cout % CBK == 0 (a k-step never
+// spans two taps). 1-D grid: n tile fastest, classes heaviest first.
+template <typename T, int BM, int BN, int WAVES_M, int WAVES_N>
+__global__ __launch_bounds__(kBlock) void conv_dgrad_phase_kernel(
+    const T* __restrict__ dy, const T* __restrict__ w_t, T* __restrict__ dx,
+    ConvShape sh, dgph::Map mp) {
+  constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
+  constexpr int MF = WM / CFRAG, NF = WN / CFRAG;
+  static_assert(BM <= kBlock, "one thread per row fills row_px");
+  __shared__ T a_lds[2][BM * lds_row_elems<T>()];
+  __shared__ T b_lds[2][BN * lds_row_elems<T>()];
+  __shared__ int row_px[BM];     // flat input pixel of a tile row, -1 past the class
+  const int Ntot = sh.Cin;
+  const int Ktot = sh.KH * sh.KW * sh.Cout;
+  const int n_tiles = (Ntot + BN - 1) / BN;
+  const dgph::Tile tile = dgph::block_tile(mp, blockIdx.x, n_tiles, sh.swz);
+  const dgph::Class& cls = mp.cls[tile.cls];
+  const int r0 = tile.m_tile * BM, n0 = tile.n_tile * BN;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wid = threadIdx.x / kWave;
+  const int wm0 = (wid / WAVES_N) * WM, wn0 = (wid % WAVES_N) * WN;
+  f32x4 acc[MF][NF] = {};
+  const int nk = cls.ntaps * (sh.Cout / CBK);   // 0 for a class without taps
+  if (threadIdx.x < BM) {
+    const int r = r0 + threadIdx.x;
+    row_px[threadIdx.x] = r < cls.rows ? dgph::row_pixel(mp, cls, r) : -1;
+  }
+  DgradPhaseAStager<T, BM> sa;
+  sa.init(cls, r0);
+  int tap = cls.tap0, co0 = 0;                  // block-uniform k cursor
+  auto stage = [&](int buf) {
+    const dgph::Tap tp = mp.taps[tap];
+    sa.stage(a_lds[buf], dy, sh, tp.dh, tp.dw, co0);
+    stage_fwd_B<T, BN>(b_lds[buf], w_t, n0,
+                       (tp.kh * sh.KW + tp.kw) * sh.Cout + co0, Ntot, Ktot, Ktot);
+    co0 += CBK;
+    if (co0 == sh.Cout) { co0 = 0; ++tap; }
+  };
+  if (nk > 0) stage(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) stage(cur ^ 1);
+    conv_mma<T, MF, NF>(a_lds[cur], b_lds[cur], acc, lane, wm0, wn0);
+    __syncthreads();
+  }
+  const int col_in_frag = lane & 15, row_base = (lane >> 4) * 4;
+#pragma unroll
+  for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int px = row_px[wm0 + mf * CFRAG + row_base + r];
+      if (px < 0) continue;
+#pragma unroll
+      for (int nf = 0; nf < NF; ++nf) {
+        const int col = n0 + wn0 + nf * CFRAG + col_in_frag;
+        if (col < Ntot) dx[(long long)px * Ntot + col] = (T)acc[mf][nf][r];
+      }
+    }
+}
+
 // Split-K over pixels (see launcher): partials -> fp32 atomics.
 template <typename T, int BM, int BN, int WAVES_M, int WAVES_N>
 __global__ __launch_bounds__(kBlock) void conv_wgrad_kernel(
@@ -600,6 +711,10 @@ __global__ __launch_bounds__(kBlock) void conv_wgrad_kernel(
       const T*, const T*, T*, ConvShape);                                   \
   template __global__ void conv_dgrad_kernel<T, 128, 64, 4, 1, false>(      \
       const T*, const T*, T*, ConvShape);                                   \
+  template __global__ void conv_dgrad_phase_kernel<T, 128, 128, 2, 2>(      \
+      const T*, const T*, T*, ConvShape, dgph::Map);                        \
+  template __global__ void conv_dgrad_phase_kernel<T, 128, 64, 4, 1>(       \
+      const T*, const T*, T*, ConvShape, dgph::Map);                        \
   template __global__ void conv_wgrad_kernel<T, 128, 128, 2, 2>(            \
       const T*, const T*, float*, ConvShape, long long);                    \
   template __global__ void conv_wgrad_kernel<T, 64, 128, 1, 4>(             \
@@ -654,6 +769,19 @@ void launch_conv_dgrad(bool is_bf16, const void* dy, const void* w, void* dx,
   const bool narrow = Cin <= 64;
   const bool fast = (Cout % CBK) == 0;
   const int BN_ = narrow ? 64 : 128;
+  // stride 2: phase-decomposed, only the live taps of each parity class
+  if (dgph::eligible(N, H, W, Cout, KH, KW, stride, pad, CBK)) {
+    const dgph::Map mp = dgph::make_map(N, H, W, KH, KW, pad, 128);
+    dim3 pgrid((unsigned)(mp.m_tiles * ((Cin + BN_ - 1) / BN_)));
+    #define DGP(T, BM, BN, WM, WN)                                          \
+      hipLaunchKernelGGL((conv_dgrad_phase_kernel<T, BM, BN, WM, WN>),      \
+                         pgrid, dim3(kBlock), 0, s, (const T*)dy,           \
+                         (const T*)w, (T*)dx, sh, mp)
+    if (is_bf16) { if (narrow) DGP(bf16, 128, 64, 4, 1); else DGP(bf16, 128, 128, 2, 2); }
+    else { if (narrow) DGP(float, 128, 64, 4, 1); else DGP(float, 128, 128, 2, 2); }
+    #undef DGP
+    return;
+  }
   dim3 grid((Cin + BN_ - 1) / BN_, (M + 127) / 128);
   #define DG(T, BM, BN, WM, WN, F)                                          \
     hipLaunchKernelGGL((conv_dgrad_kernel<T, BM, BN, WM, WN, F>), grid,     \

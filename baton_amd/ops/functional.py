@@ -139,18 +139,25 @@ class Conv2dFn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         stride, pad = ctx.stride, ctx.pad
         dy = dy.contiguous()
+        # the stem's x is the data batch: nobody wants its dx
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        dx = dw = None
         if _on_gpu(dy):
             ops = require_hip()
-            dx = ops.conv_dgrad(dy, w, x.shape[1], x.shape[2], stride, pad)
-            dw = ops.conv_wgrad(dy, x, w.shape[1], w.shape[2], stride, pad, False)
+            if need_dx:
+                dx = ops.conv_dgrad(dy, w, x.shape[1], x.shape[2], stride, pad)
+            if need_dw:
+                dw = ops.conv_wgrad(dy, x, w.shape[1], w.shape[2], stride, pad, False)
         else:
             xn = x.permute(0, 3, 1, 2).float()
             wn = w.permute(0, 3, 1, 2).float()
             dyn = dy.permute(0, 3, 1, 2).float()
-            dxn = torch.nn.grad.conv2d_input(xn.shape, wn, dyn, stride=stride, padding=pad)
-            dwn = torch.nn.grad.conv2d_weight(xn, wn.shape, dyn, stride=stride, padding=pad)
-            dx = dxn.permute(0, 2, 3, 1).contiguous().to(x.dtype)
-            dw = dwn.permute(0, 2, 3, 1).contiguous().to(w.dtype)
+            if need_dx:
+                dxn = torch.nn.grad.conv2d_input(xn.shape, wn, dyn, stride=stride, padding=pad)
+                dx = dxn.permute(0, 2, 3, 1).contiguous().to(x.dtype)
+            if need_dw:
+                dwn = torch.nn.grad.conv2d_weight(xn, wn.shape, dyn, stride=stride, padding=pad)
+                dw = dwn.permute(0, 2, 3, 1).contiguous().to(w.dtype)
         return dx, dw, None, None
 
 

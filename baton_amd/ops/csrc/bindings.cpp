@@ -25,6 +25,14 @@ void check_compute(const at::Tensor& t, const char* name) {
 
 hipStream_t stream() { return at::hip::getCurrentHIPStream().stream(); }
 
+// Refuse what no kernel is instantiated for, before anything is allocated
+// or launched.
+void check_supported(const GemmProblem& p, const GemmPlan& pl) {
+  const char* why = gemm_unsupported(p, pl);
+  TORCH_CHECK(why == nullptr, "gemm: unsupported combination: ", why ? why : "",
+              " (layout ", p.layout, ", ", kGemmKindName[(int)pl.kind], " plan)");
+}
+
 // Execute a plan_dense() plan: the 2-phase kernel, or G9 plus (ragged M)
 // the remainder rows under their own plan.
 void run_dense(const GemmProblem& p, const GemmPlan& pl, const void* A,
@@ -416,23 +424,31 @@ at::Tensor gemm(at::Tensor A, at::Tensor B, int64_t layout,
     TORCH_CHECK(B.size(0) == K, "TN shape mismatch");
   }
   auto out_dtype = out_f32 ? at::kFloat : A.scalar_type();
-  at::Tensor C;
-  if (C_in.defined() && C_in.numel() > 0) {
-    TORCH_CHECK(C_in.size(0) == M && C_in.size(1) == N);
-    C = C_in;
-  } else {
-    TORCH_CHECK(beta == 0.0, "beta != 0 needs C_in");
-    C = at::empty({M, N}, A.options().dtype(out_dtype));
-  }
   const float* bias_ptr = nullptr;
   if (bias.defined() && bias.numel() > 0) {
-    TORCH_CHECK(bias.scalar_type() == at::kFloat && bias.numel() == N,
-                "bias must be fp32 [N]");
+    TORCH_CHECK(bias.is_cuda() && bias.is_contiguous() &&
+                    bias.scalar_type() == at::kFloat && bias.numel() == N,
+                "bias must be fp32 [N] on GPU");
     bias_ptr = bias.data_ptr<float>();
   }
   const GemmProblem p{is_bf16(A), out_f32, (int)layout, M, N, K,
                       bias_ptr != nullptr, relu, alpha, beta, direct, 1, false};
   const GemmPlan pl = plan_gemm(p);
+  check_supported(p, pl);
+  at::Tensor C;
+  if (C_in.defined() && C_in.numel() > 0) {
+    // the kernels write through C_in as a dense [M, N] of the output dtype
+    TORCH_CHECK(C_in.is_cuda() && C_in.is_contiguous(),
+                "C_in must be a contiguous GPU tensor");
+    TORCH_CHECK(C_in.dim() == 2 && C_in.size(0) == M && C_in.size(1) == N,
+                "C_in must be [", M, ", ", N, "]");
+    TORCH_CHECK(C_in.scalar_type() == out_dtype,
+                "C_in must have the output dtype");
+    C = C_in;
+  } else {
+    TORCH_CHECK(beta == 0.0, "beta != 0 needs C_in");
+    C = at::empty({M, N}, A.options().dtype(out_dtype));
+  }
   at::Tensor Au = A, Bu = B;   // operands in the plan's layout
   if (pl.transpose_a) {
     Au = at::empty({M, K}, A.options());
@@ -465,7 +481,7 @@ at::Tensor gemm(at::Tensor A, at::Tensor B, int64_t layout,
 
 // The plan gemm() (or, with batched, gemm_batched() / bmm_strided()) would
 // execute for a problem, as a plain dict: routing is checkable on a machine
-// with no GPU.
+// with no GPU. A combination the entry points refuse raises here too.
 py::dict gemm_plan(int64_t M, int64_t N, int64_t K, int64_t layout, bool bf16,
                    bool out_f32, bool has_bias, bool relu, double alpha,
                    double beta, bool direct, int64_t nbatch, bool strided,
@@ -474,6 +490,7 @@ py::dict gemm_plan(int64_t M, int64_t N, int64_t K, int64_t layout, bool bf16,
                       has_bias, relu, alpha, beta, direct, (int)nbatch,
                       strided};
   const GemmPlan pl = batched ? plan_dense(p) : plan_gemm(p);
+  check_supported(p, pl);   // raises what the entry points would raise
   using namespace py::literals;
   auto to_dict = [](const GemmPlan& q) {
     return py::dict(
@@ -742,12 +759,8 @@ at::Tensor bmm_strided(at::Tensor A, at::Tensor B, c10::optional<at::Tensor> C_i
   TORCH_CHECK(A.is_cuda() && B.is_cuda(), "bmm_strided: GPU tensors required");
   TORCH_CHECK(A.scalar_type() == B.scalar_type());
   TORCH_CHECK(A.scalar_type() == at::kFloat || A.scalar_type() == at::kBFloat16);
-  at::Tensor C;
-  if (C_in.has_value() && C_in->defined()) {
-    C = *C_in;
-    TORCH_CHECK(C.is_cuda() && C.scalar_type() == A.scalar_type());
-  } else {
-    C = at::empty({nbatch, M, N}, A.options());
+  const bool own_c = !(C_in.has_value() && C_in->defined());
+  if (own_c) {
     scO = (int64_t)heads * M * N;
     scI = (int64_t)M * N;
     ldc = N;
@@ -756,8 +769,17 @@ at::Tensor bmm_strided(at::Tensor A, at::Tensor B, c10::optional<at::Tensor> C_i
   const GemmProblem p{is_bf16(A), false, (int)layout, (int)M, (int)N, (int)K,
                       false, false, alpha, 0.0, true, (int)nbatch,
                       gs.heads > 1 || gs.lda || gs.ldb || gs.ldc};
-  run_dense(p, plan_dense(p), A.data_ptr(), B.data_ptr(), C.data_ptr(), nullptr,
-            saO, sbO, scO, (int)b_group, gs);
+  const GemmPlan pl = plan_dense(p);
+  check_supported(p, pl);
+  at::Tensor C;
+  if (own_c) {
+    C = at::empty({nbatch, M, N}, A.options());
+  } else {
+    C = *C_in;
+    TORCH_CHECK(C.is_cuda() && C.scalar_type() == A.scalar_type());
+  }
+  run_dense(p, pl, A.data_ptr(), B.data_ptr(), C.data_ptr(), nullptr, saO, sbO,
+            scO, (int)b_group, gs);
   return C;
 }
 
@@ -782,11 +804,13 @@ at::Tensor gemm_batched(at::Tensor A, at::Tensor B, int64_t layout,
     K = A.size(1); M = A.size(2); N = B.size(2);
     TORCH_CHECK(B.size(1) == K);
   }
-  auto C = at::empty({nb, M, N},
-                     A.options().dtype(out_f32 ? at::kFloat : A.scalar_type()));
   const GemmProblem p{is_bf16(A), out_f32, (int)layout, M, N, K, false, false,
                       alpha, 0.0, true, nb, false};
-  run_dense(p, plan_dense(p), A.data_ptr(), B.data_ptr(), C.data_ptr(), nullptr,
+  const GemmPlan pl = plan_dense(p);
+  check_supported(p, pl);
+  auto C = at::empty({nb, M, N},
+                     A.options().dtype(out_f32 ? at::kFloat : A.scalar_type()));
+  run_dense(p, pl, A.data_ptr(), B.data_ptr(), C.data_ptr(), nullptr,
             (long long)A.size(1) * A.size(2), (long long)B.size(1) * B.size(2),
             (long long)M * N, (int)b_group);
   return C;

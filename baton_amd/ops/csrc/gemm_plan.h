@@ -219,3 +219,18 @@ inline GemmPlan plan_gemm(const GemmProblem& p) {
   pl.transpose_b = tb;
   return pl;
 }
+
+// Epilogue / layout combinations the dense launch ladder (launch_dense in
+// gemm.hip) has no instantiation for: the reason, or nullptr when `pl` (the
+// plan of `p`) can run. The fp32-output bf16 kernel exists for TN only and
+// the relu epilogue for NT only; launched anyway, the first would write bf16
+// into an fp32 buffer and the second would drop the relu. The split routes
+// accumulate in fp32 for every layout, so out_f32 is fine there, and with
+// fp32 inputs it changes nothing.
+inline const char* gemm_unsupported(const GemmProblem& p, const GemmPlan& pl) {
+  const bool dense = pl.kind == GemmKind::TwoPhase || pl.kind == GemmKind::G9;
+  if (p.out_f32 && p.bf16 && dense && pl.layout != 2)
+    return "out_f32 with bf16 inputs on the dense route is TN-only";
+  if (p.relu && pl.layout != 0) return "the relu epilogue is NT-only";
+  return nullptr;
+}

@@ -5,7 +5,11 @@ that pass whichever kernel runs.
 
 Expectations were derived by hand from the routing rules, not printed from
 the planner. All problems are bf16, alpha 1, beta 0, no bias / relu unless
-the row says otherwise."""
+the row says otherwise.
+
+Below the tables: the combinations no kernel exists for must raise, and a
+seeded sample of problems is checked against the launchers' preconditions.
+tests/test_gemm_exact.py checks on a GPU what the planned kernels compute."""
 
 import pytest
 
@@ -166,3 +170,192 @@ def test_plan_batched_entry_points():
           dict(kind="TwoPhase"))
     check(plan(4096, 2560, 512, NT, batched=True, nbatch=2),
           dict(kind="TwoPhase"))
+
+
+# ---- combinations without a kernel -----------------------------------------
+# The dense launch ladder has the fp32-output bf16 kernel for TN only and the
+# relu epilogue for NT only; gemm_unsupported() (gemm_plan.h) refuses the
+# rest, here and in gemm() / gemm_batched() / bmm_strided().
+
+@pytest.mark.parametrize("layout,kw", [
+    (NT, dict(out_f32=True)),
+    (NN, dict(out_f32=True)),
+    (NN, dict(relu=True)),
+    (TN, dict(relu=True)),
+    (NN, dict(relu=True, bf16=False)),
+    (NT, dict(out_f32=True, batched=True, nbatch=6)),
+    (NN, dict(out_f32=True, batched=True, nbatch=6)),
+    # G9-sized: out_f32 keeps it off G9, and the 2-phase NT has no fp32 out
+    (NT, dict(out_f32=True, M=4096, N=2560, K=512)),
+    # alpha != 1 takes a long-K shape off the split routes
+    (NT, dict(out_f32=True, alpha=0.5, M=136, N=72, K=1040)),
+])
+def test_plan_refuses_unsupported(layout, kw):
+    kw = dict(kw)
+    M, N, K = kw.pop("M", 200), kw.pop("N", 136), kw.pop("K", 104)
+    with pytest.raises(RuntimeError, match="unsupported"):
+        plan(M, N, K, layout, **kw)
+
+
+def test_plan_keeps_supported_neighbours():
+    """What sits next to the refused combinations keeps planning."""
+    # the split routes accumulate in fp32 whatever the layout
+    check(plan(136, 72, 1040, NT, out_f32=True), dict(kind="TwoPhaseSplitK"))
+    check(plan(136, 72, 1040, NN, out_f32=True), dict(kind="TwoPhaseSplitK"))
+    check(plan(256, 256, 1024, NT, out_f32=True), dict(kind="G9Slab"))
+    # native TN has the fp32-output kernel, batched too
+    check(plan(200, 136, 104, TN, out_f32=True),
+          dict(kind="TwoPhase", layout=TN))
+    check(plan(128, 64, 104, TN, out_f32=True, batched=True, nbatch=6),
+          dict(kind="TwoPhase", layout=TN))
+    # with fp32 inputs out_f32 changes nothing
+    check(plan(200, 136, 104, NT, out_f32=True, bf16=False),
+          dict(kind="TwoPhase"))
+    check(plan(200, 136, 104, NT, relu=True), dict(kind="TwoPhase"))
+
+
+# ---- launcher preconditions over a sample of problems ------------------------
+# The launchers refuse (a hard error at run time) a plan that does not tile
+# its problem. Their conditions, restated from launch_gemm_2ph,
+# launch_gemm_2ph_splitk, launch_gemm_nt_g9 and launch_gemm_nt_slab, are
+# asserted here for a seeded sample of problems instead.
+
+TILES = {(128, 128), (128, 64), (64, 128), (128, 32)}
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def draw_dim(rng, hi):
+    """Biased toward multiples of 32, 64 and 256 and their neighbours."""
+    step = rng.choice([1, 32, 32, 64, 64, 256, 256, 256])
+    if step == 1:
+        return rng.randint(1, hi)
+    v = step * rng.randint(1, hi // step) + rng.choice([-1, 0, 0, 0, 0, 1])
+    return min(max(v, 1), hi)
+
+
+def draw_problem(rng):
+    slab_shaped = rng.random() < 0.2
+    if slab_shaped:
+        # few 256-tiles, K a whole number of 32-wide k-halves
+        M, N = 256 * rng.randint(1, 8), 256 * rng.randint(1, 8)
+        K = 32 * rng.randint(16, 625)
+    else:
+        M, N, K = draw_dim(rng, 5000), draw_dim(rng, 5000), draw_dim(rng, 20000)
+    # the split routes and the re-layouts need a plain problem
+    plain = slab_shaped or rng.random() < 0.4
+    batched = not slab_shaped and rng.random() < 0.25
+    return dict(
+        M=M, N=N, K=K,
+        layout=rng.choice([NT, NN, TN]), bf16=rng.random() < 0.7,
+        out_f32=rng.random() < 0.15,
+        has_bias=not plain and rng.random() < 0.5,
+        relu=not plain and rng.random() < 0.3,
+        alpha=1.0 if plain else rng.choice([1.0, 0.5, 2.0, -1.5]),
+        beta=0.0 if plain else rng.choice([0.0, 1.0, 0.5]),
+        direct=rng.random() < 0.25, batched=batched,
+        nbatch=rng.choice([1, 2, 6, 96]) if batched else 1,
+        strided=batched and rng.random() < 0.5)
+
+
+def is_plain(p):
+    return p["beta"] == 0.0 and not p["has_bias"] and not p["relu"]
+
+
+def takes_split_route(p):
+    """gemm() splits K for plain alpha-1 problems with a small tile grid and
+    a long contraction; the batched entry points never do."""
+    tiles = cdiv(p["M"], 128) * cdiv(p["N"], 32 if p["N"] <= 32 else 128)
+    return (not p["batched"] and is_plain(p) and p["alpha"] == 1.0 and
+            tiles < 256 and p["K"] >= 1024)
+
+
+def is_refused(p):
+    # relu is not plain, so no re-layout: the effective layout is p's own.
+    # out_f32 keeps TN native, and NT / NN never become TN.
+    if p["relu"] and p["layout"] != NT:
+        return True
+    return (p["out_f32"] and p["bf16"] and p["layout"] != TN and
+            not takes_split_route(p))
+
+
+def check_two_phase(d, M, N, gz):
+    bm, bn = d["tile"]
+    assert d["tile"] in TILES
+    assert d["grid"] == (cdiv(N, bn), cdiv(M, bm), gz)
+
+
+def check_launchable(p, d):
+    M, N, K = p["M"], p["N"], p["K"]
+    kind = d["kind"]
+    relaid = d["transpose_a"] or d["transpose_b"]
+    assert d["layout"] == (NT if relaid else p["layout"])
+    if relaid:
+        assert is_plain(p) and not p["direct"] and not p["batched"]
+    if kind != "G9":
+        assert d["m_main"] == M and d["remainder"] is None
+    if kind == "TwoPhase":
+        check_two_phase(d, M, N, p["nbatch"])
+        assert d["splits"] == 1
+        return
+    if kind == "G9":
+        assert p["bf16"] and not p["out_f32"] and d["layout"] == NT
+        assert not p["relu"] and p["beta"] == 0.0
+        assert p["nbatch"] == 1 and not p["strided"]
+        assert N % 256 == 0 and K % 64 == 0 and K >= 64
+        m_main = d["m_main"]
+        assert 0 < m_main <= M and m_main % 256 == 0 and M - m_main < 256
+        assert d["tile"] == (256, 256)
+        assert d["grid"] == (N // 256, m_main // 256, 1)
+        rem = d["remainder"]
+        assert (rem is not None) == (m_main < M)
+        if rem is not None:
+            assert rem["kind"] == "TwoPhase" and rem["layout"] == NT
+            assert rem["m_main"] == M - m_main and rem["splits"] == 1
+            check_two_phase(rem, M - m_main, N, 1)
+        return
+    # the split routes: gemm() only, plain, alpha 1
+    assert takes_split_route(p)
+    splits, k_chunk = d["splits"], d["k_chunk"]
+    assert splits >= 1
+    if kind == "TwoPhaseSplitK":
+        check_two_phase(d, M, N, splits)
+        assert k_chunk >= 32 and k_chunk % 32 == 0
+        assert splits * k_chunk >= K > (splits - 1) * k_chunk
+        return
+    assert kind in ("G9Slab", "G8Slab")
+    assert p["bf16"] and d["layout"] == NT
+    assert M % 256 == 0 and N % 256 == 0
+    assert d["tile"] == (256, 256)
+    assert d["grid"] == (N // 256, M // 256, splits)
+    assert splits * k_chunk == K and k_chunk >= 64
+    assert k_chunk % (64 if kind == "G9Slab" else 32) == 0
+
+
+def test_plan_sweep_launcher_preconditions():
+    import random
+
+    rng = random.Random(20240611)
+    kinds, refused = {}, 0
+    for _ in range(2000):
+        p = draw_problem(rng)
+        args = (p["M"], p["N"], p["K"], p["layout"])
+        kw = {k: v for k, v in p.items() if k not in ("M", "N", "K", "layout")}
+        if is_refused(p):
+            refused += 1
+            with pytest.raises(RuntimeError, match="unsupported"):
+                plan(*args, **kw)
+            continue
+        d = plan(*args, **kw)
+        try:
+            check_launchable(p, d)
+        except AssertionError as e:
+            raise AssertionError(f"{p} -> {d}: {e}") from e
+        kinds[d["kind"]] = kinds.get(d["kind"], 0) + 1
+    print(f"sweep: {kinds}, {refused} refused")
+    # the sample reaches every route
+    assert set(kinds) == {"TwoPhase", "TwoPhaseSplitK", "G9", "G9Slab",
+                          "G8Slab"}
+    assert refused > 50

@@ -2,9 +2,10 @@
 //
 // Validate tensors (contiguous, dtype, device), allocate outputs and
 // workspaces, pull raw pointers and the current HIP stream, call the
-// launchers (launchers.h). Every FLOP is in the .hip kernels; the one
-// piece of policy executed here is the GEMM plan (gemm_plan.h): gemm()
-// allocates what the plan asks for and launches what it names.
+// launchers (launchers.h). Every FLOP is in the .hip kernels; the policy
+// executed here is the GEMM plan (gemm_plan.h) and the conv route
+// (conv_route.h): gemm() and conv_fwd() / conv_dgrad() / conv_wgrad()
+// allocate what the plan asks for and launch what it names.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -73,6 +74,15 @@ void run_splitk(const GemmPlan& pl, const at::Tensor& A, const at::Tensor& B,
   TORCH_CHECK(launch_gemm_2ph_splitk(pl, is_bf16(A), A.data_ptr(), B.data_ptr(),
                                      out.data_ptr<float>(), M, N, K, stream()),
               "gemm: split-K plan does not fit ", M, "x", N, "x", K);
+}
+
+// A conv launcher that refuses its route is a bug in conv_route.h, never a
+// reason to run another kernel.
+void check_launched(bool ok, const ConvProblem& p, const ConvRoute& rt) {
+  TORCH_CHECK(ok, "conv ", kConvOpName[(int)p.op], ": ",
+              kConvKindName[(int)rt.kind], " route does not fit N=", p.N,
+              " H=", p.H, " W=", p.W, " Cin=", p.Cin, " Cout=", p.Cout, " K=",
+              p.KH, "x", p.KW, " stride=", p.stride, " pad=", p.pad);
 }
 
 }  // namespace
@@ -519,25 +529,29 @@ at::Tensor conv_fwd(at::Tensor x, at::Tensor w, int64_t stride, int64_t pad) {
   int N = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3);
   int Cout = w.size(0), KH = w.size(1), KW = w.size(2);
   TORCH_CHECK(w.size(3) == Cin, "conv channel mismatch");
-  int HO = (H + 2 * (int)pad - KH) / (int)stride + 1;
-  int WO = (W + 2 * (int)pad - KW) / (int)stride + 1;
-  auto y = at::empty({N, HO, WO, Cout}, x.options());
-  if (is_bf16(x) && KH == 3 && KW == 3 && stride == 1 && pad == 1 &&
-      (long long)H * W % 128 == 0 && 128 % W == 0 && Cin % 32 == 0 &&
-      Cout % 64 == 0) {
-    // fragment-ordered weight image: one wave B-load = contiguous 1 KiB
-    auto wf = w.view({Cout / 16, 16, 9, Cin / 32, 4, 8})
-                  .permute({2, 3, 0, 4, 1, 5}).contiguous();
-    if (launch_conv_halo_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), N, H,
-                             W, Cin, Cout, stream()))
-      return y;
+  const ConvProblem p{ConvOp::Fwd, is_bf16(x), N, H, W, Cin, Cout, KH, KW,
+                      (int)stride, (int)pad};
+  const ConvRoute rt = conv_route(p);
+  auto y = at::empty({N, rt.HO, rt.WO, Cout}, x.options());
+  bool ok = false;
+  switch (rt.kind) {
+    case ConvKind::Halo: {
+      // fragment-ordered weight image: one wave B-load = contiguous 1 KiB
+      auto wf = w.view({Cout / 16, 16, 9, Cin / 32, 4, 8})
+                    .permute({2, 3, 0, 4, 1, 5}).contiguous();
+      ok = launch_conv_halo(rt, p, x.data_ptr(), wf.data_ptr(), y.data_ptr(),
+                            stream());
+      break;
+    }
+    case ConvKind::Conv8:
+      ok = launch_conv_8ph(rt, p, x.data_ptr(), w.data_ptr(), y.data_ptr(),
+                           stream());
+      break;
+    default:
+      ok = launch_conv_fwd(rt, p, x.data_ptr(), w.data_ptr(), y.data_ptr(),
+                           stream());
   }
-  if (is_bf16(x) &&
-      launch_conv_fwd_8ph(x.data_ptr(), w.data_ptr(), y.data_ptr(), N, H, W,
-                          Cin, Cout, KH, KW, (int)stride, (int)pad, stream()))
-    return y;
-  launch_conv_fwd(is_bf16(x), x.data_ptr(), w.data_ptr(), y.data_ptr(), N, H, W,
-                  Cin, Cout, KH, KW, (int)stride, (int)pad, stream());
+  check_launched(ok, p, rt);
   return y;
 }
 
@@ -552,23 +566,27 @@ at::Tensor conv_dgrad(at::Tensor dy, at::Tensor w, int64_t H, int64_t W,
   // <= few-MB tensor is microseconds
   auto wt = w.permute({3, 1, 2, 0}).contiguous();
   auto dx = at::empty({N, H, W, Cin}, dy.options());
-  if (is_bf16(dy) && KH == 3 && KW == 3 && stride == 1 && pad == 1 &&
-      (long long)H * W % 128 == 0 && 128 % W == 0 && Cout % 32 == 0 &&
-      Cin % 64 == 0) {
-    auto wf = wt.view({Cin / 16, 16, 9, Cout / 32, 4, 8})
-                  .permute({2, 3, 0, 4, 1, 5}).contiguous();
-    if (launch_conv_halo_dgrad(dy.data_ptr(), wf.data_ptr(), dx.data_ptr(), N,
-                               (int)H, (int)W, Cin, Cout, stream()))
-      return dx;
+  const ConvProblem p{ConvOp::Dgrad, is_bf16(dy), N, (int)H, (int)W, Cin, Cout,
+                      KH, KW, (int)stride, (int)pad};
+  const ConvRoute rt = conv_route(p);
+  bool ok = false;
+  switch (rt.kind) {
+    case ConvKind::Halo: {
+      auto wf = wt.view({Cin / 16, 16, 9, Cout / 32, 4, 8})
+                    .permute({2, 3, 0, 4, 1, 5}).contiguous();
+      ok = launch_conv_halo(rt, p, dy.data_ptr(), wf.data_ptr(), dx.data_ptr(),
+                            stream());
+      break;
+    }
+    case ConvKind::Conv8:
+      ok = launch_conv_8ph(rt, p, dy.data_ptr(), wt.data_ptr(), dx.data_ptr(),
+                           stream());
+      break;
+    default:
+      ok = launch_conv_dgrad(rt, p, dy.data_ptr(), wt.data_ptr(),
+                             dx.data_ptr(), stream());
   }
-  if (is_bf16(dy) &&
-      launch_conv_dgrad_8ph(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), N,
-                            (int)H, (int)W, Cin, Cout, KH, KW, (int)stride,
-                            (int)pad, stream()))
-    return dx;
-  launch_conv_dgrad(is_bf16(dy), dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), N,
-                    (int)H, (int)W, Cin, Cout, KH, KW, (int)stride, (int)pad,
-                    stream());
+  check_launched(ok, p, rt);
   return dx;
 }
 
@@ -581,48 +599,80 @@ at::Tensor conv_wgrad(at::Tensor dy, at::Tensor x, int64_t KH, int64_t KW,
   // split-K accumulates in fp32 (zero-init); cast down only if requested.
   long long P = (long long)dy.size(0) * dy.size(1) * dy.size(2);
   auto dw32 = at::zeros({Cout, KH, KW, Cin}, x.options().dtype(at::kFloat));
-  // 3x3 stride-1: the pixel-major kernel reads dy as it is
-  if (launch_conv_wgrad_px(is_bf16(x), dy.data_ptr(), x.data_ptr(),
-                           dw32.data_ptr(), N, H, W, Cin, Cout, (int)KH,
-                           (int)KW, (int)stride, (int)pad, stream())) {
-    // done
-  } else {
-    // every other route wants dy transposed once ([P,Cout] -> [Cout,P]) so
-    // the wgrad A operand stages direct/glds (k = pixel contiguous)
-    auto dyt = at::empty({(long long)Cout, P}, dy.options());
+  const ConvProblem p{ConvOp::Wgrad, is_bf16(x), N, H, W, Cin, Cout, (int)KH,
+                      (int)KW, (int)stride, (int)pad};
+  const ConvRoute rt = conv_route(p);
+  TORCH_CHECK(P == (long long)N * rt.HO * rt.WO, "conv_wgrad: dy has ", P,
+              " pixels, the conv gives ", (long long)N * rt.HO * rt.WO);
+  // every route but the pixel-major one wants dy transposed once ([P,Cout]
+  // -> [Cout,P]) so the wgrad A operand stages direct/glds (k = pixel
+  // contiguous)
+  at::Tensor dyt;
+  if (rt.transpose_dy) {
+    dyt = at::empty({(long long)Cout, P}, dy.options());
     launch_transpose(is_bf16(dy), dy.data_ptr(), dyt.data_ptr(), P, Cout,
                      stream());
-    if (KH == 1 && KW == 1 && stride == 1 && pad == 0) {
-      // 1x1 stride-1 wgrad IS a dense GEMM: dw[Cout,Cin] = dy_t[Cout,P] @
-      // x[P,Cin], NN, K = pixels — the split-K GEMM runs it at GEMM speed
-      // (the conv-path x gather measured ~68 TF on these shapes, the NN
-      // split-K ~250 TF). When Cout/Cin are 256-divisible, transpose x once
-      // (P is already transposed for dy) and run the 8-phase split-K slab
-      // kernel instead (r2: the rn50 bottleneck 1x1 wgrads were 12% of the
-      // step on the 2-phase atomic path).
-      int splits = 1;
-      if (is_bf16(x) && Cout % 256 == 0 && Cin % 256 == 0)
-        splits = slab_splits((long long)(Cout / 256) * (Cin / 256), (int)P);
-      if (splits > 1) {
-        auto xt = at::empty({(long long)Cin, P}, x.options());
-        launch_transpose(true, x.data_ptr(), xt.data_ptr(), P, Cin, stream());
-        run_slab(plan_slab(Cout, Cin, (int)P, splits), dyt, xt, dw32, Cout,
-                 Cin, (int)P);
-      } else {
-        run_splitk(plan_splitk(1, Cout, Cin, (int)P), dyt, x, dw32, Cout, Cin,
-                   (int)P);
-      }
-    } else {
-      launch_conv_wgrad(is_bf16(x), dyt.data_ptr(), x.data_ptr(),
-                        dw32.data_ptr(), N, H, W, Cin, Cout, (int)KH, (int)KW,
-                        (int)stride, (int)pad, stream());
+  }
+  switch (rt.kind) {
+    case ConvKind::WgradPx:
+      check_launched(launch_conv_wgrad_px(rt, p, dy.data_ptr(), x.data_ptr(),
+                                          dw32.data_ptr(), stream()),
+                     p, rt);
+      break;
+    case ConvKind::Wgrad1x1Slab: {
+      // dw[Cout,Cin] = dy_t[Cout,P] @ x_t[Cin,P]^T on the 8-wave slab kernel
+      auto xt = at::empty({(long long)Cin, P}, x.options());
+      launch_transpose(true, x.data_ptr(), xt.data_ptr(), P, Cin, stream());
+      run_slab(rt.gemm, dyt, xt, dw32, Cout, Cin, (int)P);
+      break;
     }
+    case ConvKind::Wgrad1x1SplitK:
+      // dw[Cout,Cin] = dy_t[Cout,P] @ x[P,Cin], NN split-K
+      run_splitk(rt.gemm, dyt, x, dw32, Cout, Cin, (int)P);
+      break;
+    default:
+      check_launched(launch_conv_wgrad(rt, p, dyt.data_ptr(), x.data_ptr(),
+                                       dw32.data_ptr(), stream()),
+                     p, rt);
   }
   if (out_f32 || x.scalar_type() == at::kFloat) return dw32;
   auto dw = at::empty({Cout, KH, KW, Cin}, x.options());
   launch_cast_copy(true, dw.data_ptr(), dw32.data_ptr<float>(), dw.numel(),
                    stream());
   return dw;
+}
+
+// The route conv_fwd() / conv_dgrad() / conv_wgrad() would execute for a
+// problem, as a plain dict: routing is checkable on a machine with no GPU.
+py::dict conv_route_py(const std::string& op, int64_t N, int64_t H, int64_t W,
+                       int64_t Cin, int64_t Cout, int64_t KH, int64_t KW,
+                       int64_t stride, int64_t pad, bool bf16) {
+  using namespace py::literals;
+  int o = -1;
+  for (int i = 0; i < 3; ++i)
+    if (op == kConvOpName[i]) o = i;
+  TORCH_CHECK(o >= 0, "conv_route: op must be fwd, dgrad or wgrad");
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 &&
+                  KW > 0 && stride > 0 && pad >= 0,
+              "conv_route: bad shape");
+  const ConvProblem p{(ConvOp)o, bf16, (int)N, (int)H, (int)W, (int)Cin,
+                      (int)Cout, (int)KH, (int)KW, (int)stride, (int)pad};
+  TORCH_CHECK(H + 2 * pad >= KH && W + 2 * pad >= KW,
+              "conv_route: kernel larger than the padded image");
+  const ConvRoute rt = conv_route(p);
+  return py::dict(
+      "kind"_a = kConvKindName[(int)rt.kind],
+      "out_hw"_a = py::make_tuple(rt.HO, rt.WO),
+      "tile"_a = py::make_tuple(rt.bm, rt.bn), "fast"_a = rt.fast,
+      "grid"_a = py::make_tuple(rt.grid_x, rt.grid_y, rt.grid_z),
+      "splits"_a = rt.splits, "p_chunk"_a = rt.p_chunk,
+      "use_swz"_a = rt.use_swz, "transpose_dy"_a = rt.transpose_dy,
+      "transpose_x"_a = rt.transpose_x,
+      // the GEMM kernel of the 1x1 wgrad routes (gemm_plan.h), else None
+      "gemm_kind"_a = (rt.kind == ConvKind::Wgrad1x1SplitK ||
+                       rt.kind == ConvKind::Wgrad1x1Slab)
+                          ? py::object(py::str(kGemmKindName[(int)rt.gemm.kind]))
+                          : py::object(py::none()));
 }
 
 
@@ -1104,6 +1154,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("inverse") = false);
   m.def("silu_mul_fwd", &silu_mul_fwd);
   m.def("silu_mul_bwd", &silu_mul_bwd);
+  m.def("conv_route", &conv_route_py, py::arg("op"), py::arg("N"),
+        py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"),
+        py::arg("KH"), py::arg("KW"), py::arg("stride"), py::arg("pad"),
+        py::arg("bf16") = true);
   m.def("conv_fwd", &conv_fwd);
   m.def("conv_dgrad", &conv_dgrad);
   m.def("conv_wgrad", &conv_wgrad);

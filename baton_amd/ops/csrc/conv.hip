@@ -102,7 +102,10 @@ struct FwdAStager {
       // (block-uniform condition: the whole 128-pixel tile is in bounds).
       // ci carries the PER-THREAD scalar-path offset kc; the glds helper
       // wants the block-uniform tile base, so strip kc back out.
-      if (sh.KH == 1 && sh.stride == 1 && full_ && (sh.Cin % 8) == 0) {
+      // A 1xKW kernel or a padded 1x1 is NOT one: its rows are shifted /
+      // padded pixels, and its output has more rows than x has pixels.
+      if (sh.KH == 1 && sh.KW == 1 && sh.pad == 0 && sh.stride == 1 && full_ &&
+          (sh.Cin % 8) == 0) {
         stage_glds_rows<ROWS>((bf16*)lds, (const bf16*)x, sh.Cin,
                               (long long)m0_, ci - kc);
         ci += CBK;
@@ -724,34 +727,41 @@ INST_CONV(bf16)
 INST_CONV(float)
 
 // ---- launchers -------------------------------------------------------------
+// conv_route.h decides; these launch what the route names and refuse a
+// route of another kind or one that does not cover the problem.
 #include "launchers.h"
 
-static ConvShape make_shape(int N, int H, int W, int Cin, int Cout, int KH,
-                            int KW, int stride, int pad) {
+static ConvShape make_shape(const ConvRoute& rt, const ConvProblem& p) {
   ConvShape sh;
-  sh.N = N; sh.H = H; sh.W = W; sh.Cin = Cin; sh.Cout = Cout;
-  sh.KH = KH; sh.KW = KW; sh.stride = stride; sh.pad = pad;
-  sh.HO = (H + 2 * pad - KH) / stride + 1;
-  sh.WO = (W + 2 * pad - KW) / stride + 1;
-  // XCD swizzle only past the 256 MiB L3 (see gemm.hip)
-  long long act = (long long)N * H * W * Cin + (long long)N * sh.HO * sh.WO * Cout;
-  sh.swz = act * 2 > (200LL << 20) ? 1 : 0;
+  sh.N = p.N; sh.H = p.H; sh.W = p.W; sh.Cin = p.Cin; sh.Cout = p.Cout;
+  sh.KH = p.KH; sh.KW = p.KW; sh.stride = p.stride; sh.pad = p.pad;
+  sh.HO = rt.HO;
+  sh.WO = rt.WO;
+  sh.swz = rt.use_swz;
   return sh;
 }
 
-void launch_conv_fwd(bool is_bf16, const void* x, const void* w, void* y,
-                     int N, int H, int W, int Cin, int Cout, int KH, int KW,
-                     int stride, int pad, hipStream_t s) {
-  ConvShape sh = make_shape(N, H, W, Cin, Cout, KH, KW, stride, pad);
-  long long M = (long long)N * sh.HO * sh.WO;
-  const bool narrow = Cout <= 64;
-  const bool fast = (Cin % CBK) == 0;
-  const int BN_ = narrow ? 64 : 128;
-  dim3 grid((Cout + BN_ - 1) / BN_, (M + 127) / 128);
+// HO / WO and the generic tile (128 pixels x 64 or 128 columns) are what
+// the kernels derive their indexing from
+static bool generic_tile_fits(const ConvRoute& rt, const ConvProblem& p) {
+  return rt.HO == conv_out(p.H, p.KH, p.stride, p.pad) &&
+         rt.WO == conv_out(p.W, p.KW, p.stride, p.pad) && rt.HO > 0 &&
+         rt.WO > 0 && rt.bm == 128 && (rt.bn == 64 || rt.bn == 128);
+}
+
+bool launch_conv_fwd(const ConvRoute& rt, const ConvProblem& p, const void* x,
+                     const void* w, void* y, hipStream_t s) {
+  if (rt.kind != ConvKind::Generic || p.op != ConvOp::Fwd ||
+      !generic_tile_fits(rt, p) || !conv_grid_fits(rt, p, rt.bm, rt.bn) ||
+      (rt.fast && p.Cin % CBK != 0))
+    return false;
+  const ConvShape sh = make_shape(rt, p);
+  const bool narrow = rt.bn == 64, fast = rt.fast;
+  dim3 grid(rt.grid_x, rt.grid_y);
   #define FWD(T, BM, BN, WM, WN, F)                                         \
     hipLaunchKernelGGL((conv_fwd_kernel<T, BM, BN, WM, WN, F>), grid,       \
                        dim3(kBlock), 0, s, (const T*)x, (const T*)w, (T*)y, sh)
-  if (is_bf16) {
+  if (p.bf16) {
     if (narrow) { if (fast) FWD(bf16, 128, 64, 4, 1, true); else FWD(bf16, 128, 64, 4, 1, false); }
     else { if (fast) FWD(bf16, 128, 128, 2, 2, true); else FWD(bf16, 128, 128, 2, 2, false); }
   } else {
@@ -759,34 +769,41 @@ void launch_conv_fwd(bool is_bf16, const void* x, const void* w, void* y,
     else { if (fast) FWD(float, 128, 128, 2, 2, true); else FWD(float, 128, 128, 2, 2, false); }
   }
   #undef FWD
+  return true;
 }
 
-void launch_conv_dgrad(bool is_bf16, const void* dy, const void* w, void* dx,
-                       int N, int H, int W, int Cin, int Cout, int KH, int KW,
-                       int stride, int pad, hipStream_t s) {
-  ConvShape sh = make_shape(N, H, W, Cin, Cout, KH, KW, stride, pad);
-  long long M = (long long)N * H * W;
-  const bool narrow = Cin <= 64;
-  const bool fast = (Cout % CBK) == 0;
-  const int BN_ = narrow ? 64 : 128;
+bool launch_conv_dgrad(const ConvRoute& rt, const ConvProblem& p,
+                       const void* dy, const void* w, void* dx,
+                       hipStream_t s) {
+  if (p.op != ConvOp::Dgrad || !generic_tile_fits(rt, p)) return false;
+  const ConvShape sh = make_shape(rt, p);
+  const bool narrow = rt.bn == 64;
   // stride 2: phase-decomposed, only the live taps of each parity class
-  if (dgph::eligible(N, H, W, Cout, KH, KW, stride, pad, CBK)) {
-    const dgph::Map mp = dgph::make_map(N, H, W, KH, KW, pad, 128);
-    dim3 pgrid((unsigned)(mp.m_tiles * ((Cin + BN_ - 1) / BN_)));
+  if (rt.kind == ConvKind::DgradPhase) {
+    if (!conv_dgrad_phase_fits(p)) return false;
+    const dgph::Map mp = dgph::make_map(p.N, p.H, p.W, p.KH, p.KW, p.pad, 128);
+    if (rt.grid_x != mp.m_tiles * ((p.Cin + rt.bn - 1) / rt.bn) ||
+        rt.grid_y != 1 || rt.grid_z != 1)
+      return false;
+    dim3 pgrid((unsigned)rt.grid_x);
     #define DGP(T, BM, BN, WM, WN)                                          \
       hipLaunchKernelGGL((conv_dgrad_phase_kernel<T, BM, BN, WM, WN>),      \
                          pgrid, dim3(kBlock), 0, s, (const T*)dy,           \
                          (const T*)w, (T*)dx, sh, mp)
-    if (is_bf16) { if (narrow) DGP(bf16, 128, 64, 4, 1); else DGP(bf16, 128, 128, 2, 2); }
+    if (p.bf16) { if (narrow) DGP(bf16, 128, 64, 4, 1); else DGP(bf16, 128, 128, 2, 2); }
     else { if (narrow) DGP(float, 128, 64, 4, 1); else DGP(float, 128, 128, 2, 2); }
     #undef DGP
-    return;
+    return true;
   }
-  dim3 grid((Cin + BN_ - 1) / BN_, (M + 127) / 128);
+  if (rt.kind != ConvKind::Generic || !conv_grid_fits(rt, p, rt.bm, rt.bn) ||
+      (rt.fast && p.Cout % CBK != 0))
+    return false;
+  const bool fast = rt.fast;
+  dim3 grid(rt.grid_x, rt.grid_y);
   #define DG(T, BM, BN, WM, WN, F)                                          \
     hipLaunchKernelGGL((conv_dgrad_kernel<T, BM, BN, WM, WN, F>), grid,     \
                        dim3(kBlock), 0, s, (const T*)dy, (const T*)w, (T*)dx, sh)
-  if (is_bf16) {
+  if (p.bf16) {
     if (narrow) { if (fast) DG(bf16, 128, 64, 4, 1, true); else DG(bf16, 128, 64, 4, 1, false); }
     else { if (fast) DG(bf16, 128, 128, 2, 2, true); else DG(bf16, 128, 128, 2, 2, false); }
   } else {
@@ -794,31 +811,34 @@ void launch_conv_dgrad(bool is_bf16, const void* dy, const void* w, void* dx,
     else { if (fast) DG(float, 128, 128, 2, 2, true); else DG(float, 128, 128, 2, 2, false); }
   }
   #undef DG
+  return true;
 }
 
-void launch_conv_wgrad(bool is_bf16, const void* dy, const void* x, void* dw,
-                       int N, int H, int W, int Cin, int Cout, int KH, int KW,
-                       int stride, int pad, hipStream_t s) {
+bool launch_conv_wgrad(const ConvRoute& rt, const ConvProblem& p,
+                       const void* dy, const void* x, void* dw,
+                       hipStream_t s) {
   // dw is ALWAYS the fp32 accumulation buffer (bindings allocate zeroed).
-  ConvShape sh = make_shape(N, H, W, Cin, Cout, KH, KW, stride, pad);
-  int Ntot = KH * KW * Cin;
-  const bool narrow_m = Cout <= 64;
-  const int BM_ = narrow_m ? 64 : 128;
-  int tiles_x = (Ntot + 127) / 128;
-  int tiles_y = (Cout + BM_ - 1) / BM_;
-  long long Ptot = (long long)N * sh.HO * sh.WO;
-  int target = 512 / (tiles_x * tiles_y);
-  if (target < 1) target = 1;
-  long long max_splits = (Ptot + CBK - 1) / CBK;
-  int splits = (int)(max_splits < target ? max_splits : target);
-  long long p_chunk = ((Ptot + splits - 1) / splits + CBK - 1) / CBK * CBK;
-  splits = (int)((Ptot + p_chunk - 1) / p_chunk);
-  dim3 grid(tiles_x, tiles_y, splits);
+  // The pixel slices must tile [0, P) in whole k-steps.
+  const long long Ptot = (long long)p.N * rt.HO * rt.WO;
+  if (rt.kind != ConvKind::WgradGeneric || p.op != ConvOp::Wgrad ||
+      rt.HO != conv_out(p.H, p.KH, p.stride, p.pad) ||
+      rt.WO != conv_out(p.W, p.KW, p.stride, p.pad) || Ptot <= 0 ||
+      Ptot >= (1LL << 31) || (rt.bm != 64 && rt.bm != 128) || rt.bn != 128 ||
+      rt.grid_x != (p.KH * p.KW * p.Cin + 127) / 128 ||
+      rt.grid_y != (p.Cout + rt.bm - 1) / rt.bm || rt.splits < 1 ||
+      rt.grid_z != rt.splits || rt.p_chunk < CBK || rt.p_chunk % CBK != 0 ||
+      rt.splits * rt.p_chunk < Ptot || (rt.splits - 1) * rt.p_chunk >= Ptot)
+    return false;
+  const ConvShape sh = make_shape(rt, p);
+  const bool narrow_m = rt.bm == 64;
+  const long long p_chunk = rt.p_chunk;
+  dim3 grid(rt.grid_x, rt.grid_y, rt.splits);
   #define WG(T, BM, BN, WM, WN)                                             \
     hipLaunchKernelGGL((conv_wgrad_kernel<T, BM, BN, WM, WN>), grid,        \
                        dim3(kBlock), 0, s, (const T*)dy, (const T*)x,       \
                        (float*)dw, sh, p_chunk)
-  if (is_bf16) { if (narrow_m) WG(bf16, 64, 128, 1, 4); else WG(bf16, 128, 128, 2, 2); }
+  if (p.bf16) { if (narrow_m) WG(bf16, 64, 128, 1, 4); else WG(bf16, 128, 128, 2, 2); }
   else { if (narrow_m) WG(float, 64, 128, 1, 4); else WG(float, 128, 128, 2, 2); }
   #undef WG
+  return true;
 }

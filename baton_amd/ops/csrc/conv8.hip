@@ -14,9 +14,12 @@
 // lane-linear. The XOR slot swizzle rides on the source k-offset exactly
 // as in gemm8.
 //
-// Eligibility (launcher-checked): bf16, stride 1 (dgrad) / any (fwd),
-// channels % 32 == 0, pixels % 256 == 0, Cout (fwd) / Cin (dgrad) % 256
-// == 0, K % 64 == 0. Everything else keeps the 2-phase kernels.
+// Eligibility (conv8_fits() in conv_route.h, launcher-checked): bf16,
+// stride 1 (dgrad) / any (fwd), contracted channels % 32 == 0, Cout (fwd) /
+// Cin (dgrad) % 256 == 0, K % 64 == 0. The pixel count need NOT be a
+// multiple of 256: the A stagers send rows past M to the zero page and the
+// epilogue skips them (`rok`, `row < Mtot`). The router additionally wants
+// >= 256 blocks; everything else keeps the 2-phase kernels.
 #include "common.h"
 
 namespace c8 {
@@ -314,41 +317,25 @@ __global__ __launch_bounds__(THREADS) void conv_dgrad_8ph_kernel(
 
 #include "launchers.h"
 
-// fwd: y[M=N*HO*WO, Cout]; eligible when Cout % 256 == 0, Cin % 32 == 0,
-// K % 64 == 0 (k-halves pair up) and the pixel grid fills the chip.
-bool launch_conv_fwd_8ph(const void* x, const void* w, void* y, int N, int H,
-                         int W, int Cin, int Cout, int KH, int KW, int stride,
-                         int pad, hipStream_t s) {
-  const int HO = (H + 2 * pad - KH) / stride + 1;
-  const int WO = (W + 2 * pad - KW) / stride + 1;
-  const long long M = (long long)N * HO * WO;
-  const int Ktot = KH * KW * Cin;
-  if (Cout % c8::TN != 0 || Cin % 32 != 0 || Ktot % 64 != 0) return false;
-  const long long mt = (M + c8::TM - 1) / c8::TM;
-  if (mt * (Cout / c8::TN) < 256) return false;   // 2-phase fills better
-  c8::Shape sh{N, H, W, Cin, Cout, KH, KW, stride, pad, HO, WO, 1};
-  dim3 grid(Cout / c8::TN, (unsigned)mt);
-  hipLaunchKernelGGL(c8::conv_fwd_8ph_kernel, grid, dim3(c8::THREADS), 0, s,
-                     (const bf16*)x, (const bf16*)w, (bf16*)y, sh);
-  return true;
-}
-
-// dgrad: dx[M=N*H*W, Cin]; stride-1 only (strided dgrad keeps the 2-phase
-// one-tap stager). w_t is the [Cin, KH*KW*Cout] transposed copy.
-bool launch_conv_dgrad_8ph(const void* dy, const void* w_t, void* dx, int N,
-                           int H, int W, int Cin, int Cout, int KH, int KW,
-                           int stride, int pad, hipStream_t s) {
-  if (stride != 1) return false;
-  const int HO = (H + 2 * pad - KH) / stride + 1;
-  const int WO = (W + 2 * pad - KW) / stride + 1;
-  const long long M = (long long)N * H * W;
-  const int Ktot = KH * KW * Cout;
-  if (Cin % c8::TN != 0 || Cout % 32 != 0 || Ktot % 64 != 0) return false;
-  const long long mt = (M + c8::TM - 1) / c8::TM;
-  if (mt * (Cin / c8::TN) < 256) return false;
-  c8::Shape sh{N, H, W, Cin, Cout, KH, KW, stride, pad, HO, WO, 1};
-  dim3 grid(Cin / c8::TN, (unsigned)mt);
-  hipLaunchKernelGGL(c8::conv_dgrad_8ph_kernel, grid, dim3(c8::THREADS), 0, s,
-                     (const bf16*)dy, (const bf16*)w_t, (bf16*)dx, sh);
+// fwd: y[M = N*HO*WO, Cout] from x and w; dgrad (stride 1): dx[M = N*H*W,
+// Cin] from dy and the [Cin, KH*KW*Cout] transposed copy w_t. What the
+// kernel needs is conv8_fits() (conv_route.h); that the pixel grid fills
+// the chip is the router's business. The last row tile may be ragged.
+bool launch_conv_8ph(const ConvRoute& rt, const ConvProblem& p, const void* a,
+                     const void* b, void* out, hipStream_t s) {
+  if (rt.kind != ConvKind::Conv8 || !conv8_fits(p) ||
+      rt.HO != conv_out(p.H, p.KH, p.stride, p.pad) ||
+      rt.WO != conv_out(p.W, p.KW, p.stride, p.pad) || rt.HO <= 0 ||
+      rt.WO <= 0 || !conv_grid_fits(rt, p, c8::TM, c8::TN))
+    return false;
+  c8::Shape sh{p.N, p.H, p.W, p.Cin, p.Cout, p.KH, p.KW, p.stride, p.pad,
+               rt.HO, rt.WO, rt.use_swz};
+  dim3 grid(rt.grid_x, rt.grid_y);
+  if (p.op == ConvOp::Fwd)
+    hipLaunchKernelGGL(c8::conv_fwd_8ph_kernel, grid, dim3(c8::THREADS), 0, s,
+                       (const bf16*)a, (const bf16*)b, (bf16*)out, sh);
+  else
+    hipLaunchKernelGGL(c8::conv_dgrad_8ph_kernel, grid, dim3(c8::THREADS), 0,
+                       s, (const bf16*)a, (const bf16*)b, (bf16*)out, sh);
   return true;
 }

@@ -146,36 +146,27 @@ __global__ __launch_bounds__(THREADS) void conv_halo_kernel(
 
 #include "launchers.h"
 
-// fwd: Y[N*H*W, Cout] = conv3x3(x, w), stride 1 pad 1.
-bool launch_conv_halo_fwd(const void* x, const void* w, void* y, int N, int H,
-                          int W, int Cin, int Cout, hipStream_t s) {
-  if ((long long)H * W % ch::PXT != 0) return false;
-  if (Cin % ch::CK != 0 || Cout % ch::NT != 0) return false;
-  const int R = ch::PXT / W;
-  if (R * W != ch::PXT || R + 2 > H + 2) return false;
-  ch::Shape sh{N, H, W, Cin, Cout, R + 2, W + 2, 1};
-  const size_t smem = 2u * (R + 2) * (W + 2) * ch::CK * sizeof(bf16);
-  if (smem > 160 * 1024) return false;
-  dim3 grid((unsigned)((long long)N * H * W / ch::PXT), Cout / ch::NT);
-  hipLaunchKernelGGL((ch::conv_halo_kernel<false>), grid, dim3(ch::THREADS),
-                     smem, s, (const bf16*)x, (const bf16*)w, (bf16*)y, sh,
-                     Cin, Cout);
-  return true;
-}
-
-// dgrad: dx[N*H*W, Cin] from dy and w_t [Cin][3][3][Cout].
-bool launch_conv_halo_dgrad(const void* dy, const void* w_t, void* dx, int N,
-                            int H, int W, int Cin, int Cout, hipStream_t s) {
-  if ((long long)H * W % ch::PXT != 0) return false;
-  if (Cout % ch::CK != 0 || Cin % ch::NT != 0) return false;
-  const int R = ch::PXT / W;
-  if (R * W != ch::PXT || R + 2 > H + 2) return false;
-  ch::Shape sh{N, H, W, Cin, Cout, R + 2, W + 2, 1};
-  const size_t smem = 2u * (R + 2) * (W + 2) * ch::CK * sizeof(bf16);
-  if (smem > 160 * 1024) return false;
-  dim3 grid((unsigned)((long long)N * H * W / ch::PXT), Cin / ch::NT);
-  hipLaunchKernelGGL((ch::conv_halo_kernel<true>), grid, dim3(ch::THREADS),
-                     smem, s, (const bf16*)dy, (const bf16*)w_t, (bf16*)dx, sh,
-                     Cout, Cin);
+// fwd: Y[N*H*W, Cout] = conv3x3(x, w), stride 1 pad 1; dgrad: dx[N*H*W,
+// Cin] from dy and w_t [Cin][3][3][Cout]. wf is the fragment-ordered weight
+// image. The kernel's needs are conv_halo_fits() (conv_route.h).
+bool launch_conv_halo(const ConvRoute& rt, const ConvProblem& p, const void* a,
+                      const void* wf, void* out, hipStream_t s) {
+  if (rt.kind != ConvKind::Halo || !conv_halo_fits(p) ||
+      rt.bm != ch::PXT || rt.bn != ch::NT ||
+      rt.grid_x != conv_rows(p) / ch::PXT ||   // pixel tiles on x here
+      rt.grid_y != conv_cols(p) / ch::NT || rt.grid_z != 1)
+    return false;
+  const int R = ch::PXT / p.W;
+  ch::Shape sh{p.N, p.H, p.W, p.Cin, p.Cout, R + 2, p.W + 2, rt.use_swz};
+  const size_t smem = 2u * (R + 2) * (p.W + 2) * ch::CK * sizeof(bf16);
+  dim3 grid(rt.grid_x, rt.grid_y);
+  if (p.op == ConvOp::Fwd)
+    hipLaunchKernelGGL((ch::conv_halo_kernel<false>), grid, dim3(ch::THREADS),
+                       smem, s, (const bf16*)a, (const bf16*)wf, (bf16*)out,
+                       sh, p.Cin, p.Cout);
+  else
+    hipLaunchKernelGGL((ch::conv_halo_kernel<true>), grid, dim3(ch::THREADS),
+                       smem, s, (const bf16*)a, (const bf16*)wf, (bf16*)out,
+                       sh, p.Cout, p.Cin);
   return true;
 }

@@ -196,13 +196,11 @@ __global__ __launch_bounds__(THREADS, 4) void wgrad_px_kernel(
       }
 }
 
+// steps = k-steps in all, sps = k-steps per grid.z slice (from the route)
 template <int W>
-static void launch_w(const bf16* dy, const bf16* x, float* dw, int N, int H,
-                     int Cin, int Cout, hipStream_t s) {
-  const long long steps = (long long)N * H * W / PXK;
-  const int gx = Cin / TILE, gy = Cout / TILE;
-  const int sps = steps_per_split(steps, gx * gy);
-  const int splits = (int)((steps + sps - 1) / sps);
+static void launch_w(const bf16* dy, const bf16* x, float* dw, int H, int Cin,
+                     int Cout, long long steps, int sps, dim3 grid,
+                     hipStream_t s) {
   constexpr int smem = NBUF * passes_of(W) * THREADS * 16;
   static bool attr_set = false;
   if (!attr_set) {
@@ -211,8 +209,8 @@ static void launch_w(const bf16* dy, const bf16* x, float* dw, int N, int H,
                               smem);
     attr_set = true;
   }
-  hipLaunchKernelGGL(wgrad_px_kernel<W>, dim3(gx, gy, splits), dim3(THREADS),
-                     smem, s, dy, x, dw, H, Cin, Cout, steps, sps);
+  hipLaunchKernelGGL(wgrad_px_kernel<W>, grid, dim3(THREADS), smem, s, dy, x,
+                     dw, H, Cin, Cout, steps, sps);
 }
 
 }  // namespace wgpx
@@ -220,23 +218,33 @@ static void launch_w(const bf16* dy, const bf16* x, float* dw, int N, int H,
 #include "launchers.h"
 
 // dw (fp32, zero-initialised by the caller) += wgrad of a 3x3 stride-1
-// pad-1 conv, dy in its natural [P][Cout] layout. Gate: wgpx::eligible() -
-// bf16, Cin % 64 == 0, Cout % 64 == 0, W in {4, 8, 16, 32}, H >= 4, and
-// with R = 32 / W rows per k-step H % R == 0 (or R % H == 0 when H < R),
-// N*H*W % 32 == 0. Returns false, launching nothing, otherwise.
-bool launch_conv_wgrad_px(bool is_bf16, const void* dy, const void* x,
-                          void* dw, int N, int H, int W, int Cin, int Cout,
-                          int KH, int KW, int stride, int pad, hipStream_t s) {
-  if (!wgpx::eligible(is_bf16, N, H, W, Cin, Cout, KH, KW, stride, pad))
+// pad-1 conv, dy in its natural [P][Cout] layout. What the kernel can run
+// is wgpx::eligible() - bf16, Cin % 64 == 0, Cout % 64 == 0, W in {4, 8, 16,
+// 32}, H >= 4, and with R = 32 / W rows per k-step H % R == 0 (or R % H == 0
+// when H < R), N*H*W % 32 == 0 - and the route's slices must tile the
+// k-steps. Returns false, launching nothing, otherwise.
+bool launch_conv_wgrad_px(const ConvRoute& rt, const ConvProblem& p,
+                          const void* dy, const void* x, void* dw,
+                          hipStream_t s) {
+  using namespace wgpx;
+  if (rt.kind != ConvKind::WgradPx || !conv_wgrad_px_fits(p)) return false;
+  const long long steps = (long long)p.N * p.H * p.W / PXK;
+  const long long sps = rt.p_chunk / PXK;
+  if (rt.bm != TILE || rt.bn != TILE || rt.grid_x != p.Cin / TILE ||
+      rt.grid_y != p.Cout / TILE || rt.splits < 1 || rt.grid_z != rt.splits ||
+      sps < 1 || rt.p_chunk % PXK != 0 || sps > (1 << 30) ||
+      rt.splits * sps < steps || (rt.splits - 1) * sps >= steps)
     return false;
   auto dyp = (const bf16*)dy;
   auto xp = (const bf16*)x;
   auto dwp = (float*)dw;
-  switch (W) {
-    case 4: wgpx::launch_w<4>(dyp, xp, dwp, N, H, Cin, Cout, s); break;
-    case 8: wgpx::launch_w<8>(dyp, xp, dwp, N, H, Cin, Cout, s); break;
-    case 16: wgpx::launch_w<16>(dyp, xp, dwp, N, H, Cin, Cout, s); break;
-    default: wgpx::launch_w<32>(dyp, xp, dwp, N, H, Cin, Cout, s); break;
+  const dim3 grid(rt.grid_x, rt.grid_y, rt.splits);
+  const int H = p.H, Cin = p.Cin, Cout = p.Cout, k = (int)sps;
+  switch (p.W) {
+    case 4: launch_w<4>(dyp, xp, dwp, H, Cin, Cout, steps, k, grid, s); break;
+    case 8: launch_w<8>(dyp, xp, dwp, H, Cin, Cout, steps, k, grid, s); break;
+    case 16: launch_w<16>(dyp, xp, dwp, H, Cin, Cout, steps, k, grid, s); break;
+    default: launch_w<32>(dyp, xp, dwp, H, Cin, Cout, steps, k, grid, s); break;
   }
   return true;
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "conv_route.h"
 #include "gemm_plan.h"
 #include "gemm_strides.h"
 
@@ -82,17 +83,22 @@ void launch_gelu_fwd(bool is_bf16, const void* x, void* y, long long n,
 void launch_gelu_bwd(bool is_bf16, const void* dy, const void* x, void* dx,
                      long long n, hipStream_t s);
 
-// conv.hip — NHWC implicit GEMM
-void launch_conv_fwd(bool is_bf16, const void* x, const void* w, void* y,
-                     int N, int H, int W, int Cin, int Cout, int KH, int KW,
-                     int stride, int pad, hipStream_t s);
-void launch_conv_dgrad(bool is_bf16, const void* dy, const void* w, void* dx,
-                       int N, int H, int W, int Cin, int Cout, int KH, int KW,
-                       int stride, int pad, hipStream_t s);
-// dy here is the TRANSPOSED [Cout][P] copy
-void launch_conv_wgrad(bool is_bf16, const void* dy, const void* x, void* dw,
-                       int N, int H, int W, int Cin, int Cout, int KH, int KW,
-                       int stride, int pad, hipStream_t s);
+// Conv launchers (conv.hip, conv8.hip, conv_halo.hip, conv_wgrad_px.hip):
+// each launches exactly the kernel, tile, grid and pixel split the ConvRoute
+// names (conv_route.h decides) and returns false, launching nothing, when
+// the route is not its kind or its kernel cannot run the problem.
+
+// conv.hip — NHWC implicit GEMM. Generic fwd; Generic / DgradPhase dgrad (w
+// is the [Cin,KH,KW,Cout] transposed copy); WgradGeneric (dy is the
+// TRANSPOSED [Cout][P] copy, dw the zeroed fp32 buffer).
+bool launch_conv_fwd(const ConvRoute& rt, const ConvProblem& p, const void* x,
+                     const void* w, void* y, hipStream_t s);
+bool launch_conv_dgrad(const ConvRoute& rt, const ConvProblem& p,
+                       const void* dy, const void* w_t, void* dx,
+                       hipStream_t s);
+bool launch_conv_wgrad(const ConvRoute& rt, const ConvProblem& p,
+                       const void* dy_t, const void* x, void* dw,
+                       hipStream_t s);
 
 // GEMM launchers (gemm.hip, gemm8.hip): each launches exactly the kernel,
 // tile, grid and K split the GemmPlan names (gemm_plan.h decides) and
@@ -182,25 +188,19 @@ bool launch_flash_bwd_dkv(const void* Q, const void* K, const void* V,
                           const long long* dks, const long long* dvs,
                           hipStream_t s);
 
-// conv8.hip — deep-pipelined 256x256 8-wave conv fwd/dgrad (bf16);
-// returns false when the shape is ineligible (caller falls back)
-bool launch_conv_fwd_8ph(const void* x, const void* w, void* y, int N, int H,
-                         int W, int Cin, int Cout, int KH, int KW, int stride,
-                         int pad, hipStream_t s);
-bool launch_conv_dgrad_8ph(const void* dy, const void* w_t, void* dx, int N,
-                           int H, int W, int Cin, int Cout, int KH, int KW,
-                           int stride, int pad, hipStream_t s);
+// conv8.hip — deep-pipelined 256x256 8-wave conv fwd / stride-1 dgrad
+// (bf16; p.op picks). b is w for fwd, the transposed w_t for dgrad.
+bool launch_conv_8ph(const ConvRoute& rt, const ConvProblem& p, const void* a,
+                     const void* b, void* out, hipStream_t s);
 
-// conv_halo.hip — shared-halo 3x3 stride-1 conv fwd/dgrad for small-channel
-// layers whose 128-px tiles stay within one image; false when ineligible
-bool launch_conv_halo_fwd(const void* x, const void* w, void* y, int N, int H,
-                          int W, int Cin, int Cout, hipStream_t s);
-bool launch_conv_halo_dgrad(const void* dy, const void* w_t, void* dx, int N,
-                            int H, int W, int Cin, int Cout, hipStream_t s);
+// conv_halo.hip — shared-halo 3x3 stride-1 conv fwd / dgrad (p.op picks) for
+// small-channel layers whose 128-px tiles stay within one image. wf is the
+// fragment-ordered image of w (fwd) / w_t (dgrad).
+bool launch_conv_halo(const ConvRoute& rt, const ConvProblem& p, const void* a,
+                      const void* wf, void* out, hipStream_t s);
 
 // conv_wgrad_px.hip — pixel-major tap-shared 3x3 stride-1 wgrad: dy in its
-// natural [P][Cout] layout, dw the zeroed fp32 buffer; false (nothing
-// launched) when wgpx::eligible() (wgrad_px_map.h) rejects the problem
-bool launch_conv_wgrad_px(bool is_bf16, const void* dy, const void* x,
-                          void* dw, int N, int H, int W, int Cin, int Cout,
-                          int KH, int KW, int stride, int pad, hipStream_t s);
+// natural [P][Cout] layout, dw the zeroed fp32 buffer
+bool launch_conv_wgrad_px(const ConvRoute& rt, const ConvProblem& p,
+                          const void* dy, const void* x, void* dw,
+                          hipStream_t s);

@@ -869,6 +869,10 @@ at::Tensor gemm_batched(at::Tensor A, at::Tensor B, int64_t layout,
 at::Tensor softmax_fwd(at::Tensor x, double scale, int64_t causal_seq) {
   check_compute(x, "x");
   int C = x.size(-1);
+  // the causal mask keeps columns c <= r % causal_seq of row r
+  TORCH_CHECK(causal_seq >= 0 && causal_seq <= C,
+              "softmax_fwd: causal_seq must be in [0, C = ", C, "], got ",
+              causal_seq);
   long long R = x.numel() / C;
   auto y = at::empty_like(x);
   launch_softmax_fwd(is_bf16(x), x.data_ptr(), y.data_ptr(), R, C,
@@ -1008,12 +1012,43 @@ std::vector<at::Tensor> silu_mul_bwd(at::Tensor dy, at::Tensor a, at::Tensor b) 
 // ---- flash attention -------------------------------------------------------
 
 namespace {
-// q/k/v/o are 4-D [B,S,heads,DH] strided VIEWS with contiguous DH
-void check_attn_view(const at::Tensor& t, const char* name) {
+// q/k/v/o are 4-D [B,S,heads,DH] strided VIEWS with contiguous DH. The
+// kernels move 16-byte vectors at element offsets that are multiples of 8
+// from (batch, seq, head) row starts, so the base pointer and the three outer
+// strides must keep every such access 16-byte aligned.
+void check_attn_view(const at::Tensor& t, const char* name,
+                     const at::Tensor& q) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, name,
               " must be a bf16 GPU tensor");
+  TORCH_CHECK(t.device() == q.device(), name, " must be on q's device");
   TORCH_CHECK(t.dim() == 4, name, " must be [B,S,h,dh]");
   TORCH_CHECK(t.stride(3) == 1, name, " head_dim must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              " must start on a 16-byte boundary");
+  TORCH_CHECK(t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
+                  t.stride(2) % 8 == 0,
+              name, " strides must be multiples of 8 elements (16 bytes)");
+}
+void check_head_dim(int64_t DH) {
+  TORCH_CHECK(DH == 32 || DH == 64 || DH == 128,
+              "flash: unsupported head_dim ", DH);
+}
+// k and v against q: same batch, sequence and head_dim, one kv head count
+// that divides q's.
+void check_kv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
+  for (int d : {0, 1, 3}) {
+    TORCH_CHECK(k.size(d) == q.size(d), "k must share q's B, S and dh: k is ",
+                k.sizes(), ", q is ", q.sizes());
+    TORCH_CHECK(v.size(d) == q.size(d), "v must share q's B, S and dh: v is ",
+                v.sizes(), ", q is ", q.sizes());
+  }
+  TORCH_CHECK(k.size(2) == v.size(2), "k and v must have the same head count");
+  TORCH_CHECK(k.size(2) > 0 && q.size(2) % k.size(2) == 0,
+              "q heads must be a multiple of kv heads");
+}
+void check_like_q(const at::Tensor& t, const char* name, const at::Tensor& q) {
+  TORCH_CHECK(t.sizes() == q.sizes(), name, " must have q's sizes ", q.sizes(),
+              ", got ", t.sizes());
 }
 void strides3(const at::Tensor& t, long long* out) {
   out[0] = t.stride(0);  // batch
@@ -1024,13 +1059,15 @@ void strides3(const at::Tensor& t, long long* out) {
 
 std::vector<at::Tensor> flash_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                   at::Tensor o, bool causal) {
-  check_attn_view(q, "q");
-  check_attn_view(k, "k");
-  check_attn_view(v, "v");
-  check_attn_view(o, "o");
+  check_attn_view(q, "q", q);
+  check_attn_view(k, "k", q);
+  check_attn_view(v, "v", q);
+  check_attn_view(o, "o", q);
+  check_head_dim(q.size(3));
+  check_kv(q, k, v);
+  check_like_q(o, "o", q);
   const int B = q.size(0), S = q.size(1), H = q.size(2), DH = q.size(3);
   const int KVH = k.size(2);
-  TORCH_CHECK(H % KVH == 0, "q heads must be a multiple of kv heads");
   const int G = H / KVH;
   auto lse = at::empty({(long long)B * H, S},
                        q.options().dtype(at::kFloat));
@@ -1048,20 +1085,32 @@ std::vector<at::Tensor> flash_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
 void flash_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                at::Tensor dout, at::Tensor lse, at::Tensor dq, at::Tensor dk,
                at::Tensor dv, bool causal) {
-  check_attn_view(q, "q");
-  check_attn_view(k, "k");
-  check_attn_view(v, "v");
-  check_attn_view(o, "o");
-  check_attn_view(dout, "dout");
-  check_attn_view(dq, "dq");
-  check_attn_view(dk, "dk");
-  check_attn_view(dv, "dv");
+  check_attn_view(q, "q", q);
+  check_attn_view(k, "k", q);
+  check_attn_view(v, "v", q);
+  check_attn_view(o, "o", q);
+  check_attn_view(dout, "dout", q);
+  check_attn_view(dq, "dq", q);
+  check_attn_view(dk, "dk", q);
+  check_attn_view(dv, "dv", q);
+  check_head_dim(q.size(3));
+  check_kv(q, k, v);
+  check_like_q(o, "o", q);
+  check_like_q(dout, "dout", q);
+  check_like_q(dq, "dq", q);
+  // dk/dv are per-q-head [B,S,H,dh] (GQA callers group-sum)
+  check_like_q(dk, "dk (per q head)", q);
+  check_like_q(dv, "dv (per q head)", q);
   const int B = q.size(0), S = q.size(1), H = q.size(2), DH = q.size(3);
   const int KVH = k.size(2);
   const int G = H / KVH;
-  TORCH_CHECK(dk.size(2) == H && dv.size(2) == H,
-              "dk/dv are per-q-head (GQA callers group-sum)");
-  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous());
+  TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() &&
+                  lse.scalar_type() == at::kFloat && lse.is_contiguous(),
+              "lse must be a contiguous fp32 tensor on q's device");
+  TORCH_CHECK(lse.dim() == 2 && lse.size(0) == (int64_t)B * H &&
+                  lse.size(1) == S,
+              "lse must be [B*H, S] = [", (int64_t)B * H, ", ", S, "], got ",
+              lse.sizes());
   auto delta = at::empty_like(lse);
   long long qs[3], ks[3], vs[3], os[3], dos[3], dqs[3], dks[3], dvs[3];
   strides3(q, qs); strides3(k, ks); strides3(v, vs); strides3(o, os);

@@ -85,6 +85,59 @@ void check_launched(bool ok, const ConvProblem& p, const ConvRoute& rt) {
               p.KH, "x", p.KW, " stride=", p.stride, " pad=", p.pad);
 }
 
+// ---- normalization argument checks ----------------------------------------
+// The norm kernels take raw pointers and trust (R, C): everything they read
+// or write is sized here, before anything is allocated or launched.
+
+struct NormShape {
+  long long R;   // rows (LayerNorm / RMSNorm) or samples per channel (BN)
+  int C;
+};
+
+// x: fp32 / bf16, contiguous, on the GPU, viewed as [R, C] with both > 0.
+// rows_fit_int: the LayerNorm kernels index rows with int.
+NormShape norm_shape(const at::Tensor& x, const char* op, bool rows_fit_int) {
+  check_compute(x, "x");
+  TORCH_CHECK(x.dim() >= 1, op, ": x must have at least one dimension");
+  const long long C = x.size(-1);
+  TORCH_CHECK(C > 0, op, ": x has C == 0 channels");
+  TORCH_CHECK(x.numel() > 0, op, ": x has no rows");
+  TORCH_CHECK(C <= INT_MAX, op, ": x has C = ", C, ", past the kernels' int");
+  const long long R = x.numel() / C;
+  TORCH_CHECK(!rows_fit_int || R <= INT_MAX, op, ": x has ", R,
+              " rows, past the kernels' int");
+  return {R, (int)C};
+}
+
+// dy / res / plus / y_post: x's sizes, dtype and device, contiguous.
+void norm_check_like_x(const at::Tensor& t, const char* name,
+                       const at::Tensor& x, const char* op) {
+  TORCH_CHECK(t.defined(), op, ": ", name, " is undefined");
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device(), op, ": ", name,
+              " must be on x's device");
+  TORCH_CHECK(t.scalar_type() == x.scalar_type(), op, ": ", name,
+              " must have x's dtype");
+  TORCH_CHECK(t.sizes() == x.sizes(), op, ": ", name, " must have x's sizes ",
+              x.sizes(), ", got ", t.sizes());
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+}
+
+// A contiguous vector of exactly n elements of dtype dt on x's device: w / b
+// (x's dtype), mean / rstd / gamma / beta / running statistics (fp32).
+void norm_check_vec(const at::Tensor& t, const char* name, const at::Tensor& x,
+                    at::ScalarType dt, long long n, const char* op) {
+  TORCH_CHECK(t.defined(), op, ": ", name, " is undefined");
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device(), op, ": ", name,
+              " must be on x's device");
+  TORCH_CHECK(t.scalar_type() == dt, op, ": ", name, " must be ",
+              dt == at::kFloat ? "fp32" : "of x's dtype");
+  TORCH_CHECK(t.numel() == n, op, ": ", name, " must have ", n,
+              " elements, got ", t.numel());
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+}
+
+bool norm_absent(const at::Tensor& t) { return !t.defined() || t.numel() == 0; }
+
 }  // namespace
 
 // ---- optim -----------------------------------------------------------------
@@ -208,11 +261,11 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
 
 std::vector<at::Tensor> ln_fwd(at::Tensor x, at::Tensor w, at::Tensor b,
                                double eps) {
-  check_compute(x, "x");
-  check_compute(w, "w");
-  check_compute(b, "b");
-  int C = x.size(-1);
-  long long R = x.numel() / C;
+  const NormShape sh = norm_shape(x, "ln_fwd", true);
+  const int C = sh.C;
+  const long long R = sh.R;
+  norm_check_vec(w, "w", x, x.scalar_type(), C, "ln_fwd");
+  norm_check_vec(b, "b", x, x.scalar_type(), C, "ln_fwd");
   auto y = at::empty_like(x);
   auto mean = at::empty({R}, x.options().dtype(at::kFloat));
   auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
@@ -226,11 +279,12 @@ std::vector<at::Tensor> ln_fwd(at::Tensor x, at::Tensor w, at::Tensor b,
 // (saved for backward / reused as the residual stream)
 std::vector<at::Tensor> ln_add_fwd(at::Tensor x, at::Tensor res, at::Tensor w,
                                    at::Tensor b, double eps) {
-  check_compute(x, "x");
-  check_compute(res, "res");
-  TORCH_CHECK(x.sizes() == res.sizes() && x.scalar_type() == res.scalar_type());
-  int C = x.size(-1);
-  long long R = x.numel() / C;
+  const NormShape sh = norm_shape(x, "ln_add_fwd", true);
+  const int C = sh.C;
+  const long long R = sh.R;
+  norm_check_like_x(res, "res", x, "ln_add_fwd");
+  norm_check_vec(w, "w", x, x.scalar_type(), C, "ln_add_fwd");
+  norm_check_vec(b, "b", x, x.scalar_type(), C, "ln_add_fwd");
   auto y = at::empty_like(x);
   auto z = at::empty_like(x);
   auto mean = at::empty({R}, x.options().dtype(at::kFloat));
@@ -244,10 +298,13 @@ std::vector<at::Tensor> ln_add_fwd(at::Tensor x, at::Tensor res, at::Tensor w,
 
 std::vector<at::Tensor> ln_bwd(at::Tensor x, at::Tensor dy, at::Tensor w,
                                at::Tensor mean, at::Tensor rstd) {
-  check_compute(x, "x");
-  check_compute(dy, "dy");
-  int C = x.size(-1);
-  long long R = x.numel() / C;
+  const NormShape sh = norm_shape(x, "ln_bwd", true);
+  const int C = sh.C;
+  const long long R = sh.R;
+  norm_check_like_x(dy, "dy", x, "ln_bwd");
+  norm_check_vec(w, "w", x, x.scalar_type(), C, "ln_bwd");
+  norm_check_vec(mean, "mean", x, at::kFloat, R, "ln_bwd");
+  norm_check_vec(rstd, "rstd", x, at::kFloat, R, "ln_bwd");
   auto dx = at::empty_like(x);
   auto dw = at::zeros({C}, x.options().dtype(at::kFloat));
   auto db = at::zeros({C}, x.options().dtype(at::kFloat));
@@ -269,17 +326,27 @@ std::vector<at::Tensor> bn_fwd_train(at::Tensor x, at::Tensor gamma,
                                      double eps, bool relu,
                                      c10::optional<at::Tensor> res_opt) {
   at::Tensor res = res_opt.value_or(at::Tensor());
+  const NormShape sh = norm_shape(x, "bn_fwd_train", false);
+  const int C = sh.C;
+  const long long M = sh.R;
   const bool has_res = res.defined() && res.numel() > 0;
   if (has_res) {
-    check_compute(res, "res");
-    TORCH_CHECK(res.sizes() == x.sizes() && res.scalar_type() == x.scalar_type(),
-                "bn res must match x");
+    norm_check_like_x(res, "res", x, "bn_fwd_train");
     TORCH_CHECK(relu, "fused residual add implies fused relu");
   }
-  check_compute(x, "x");
-  int C = x.size(-1);
-  long long M = x.numel() / C;
-  TORCH_CHECK(gamma.scalar_type() == at::kFloat, "bn gamma must be fp32");
+  norm_check_vec(gamma, "gamma", x, at::kFloat, C, "bn_fwd_train");
+  norm_check_vec(beta, "beta", x, at::kFloat, C, "bn_fwd_train");
+  // running statistics come as a pair or not at all (empty = absent)
+  const bool has_running = !norm_absent(running_mean);
+  TORCH_CHECK(has_running == !norm_absent(running_var),
+              "bn_fwd_train: running_mean and running_var must both be given "
+              "or both be absent");
+  if (has_running) {
+    norm_check_vec(running_mean, "running_mean", x, at::kFloat, C,
+                   "bn_fwd_train");
+    norm_check_vec(running_var, "running_var", x, at::kFloat, C,
+                   "bn_fwd_train");
+  }
   auto sum = at::zeros({C}, x.options().dtype(at::kFloat));
   auto sumsq = at::zeros({C}, x.options().dtype(at::kFloat));
   auto mean = at::empty({C}, x.options().dtype(at::kFloat));
@@ -287,10 +354,8 @@ std::vector<at::Tensor> bn_fwd_train(at::Tensor x, at::Tensor gamma,
   auto y = at::empty_like(x);
   launch_bn_stats(is_bf16(x), x.data_ptr(), sum.data_ptr<float>(),
                   sumsq.data_ptr<float>(), M, C, stream());
-  float* rm = running_mean.defined() && running_mean.numel() > 0
-                  ? running_mean.data_ptr<float>()
-                  : nullptr;
-  float* rv = rm ? running_var.data_ptr<float>() : nullptr;
+  float* rm = has_running ? running_mean.data_ptr<float>() : nullptr;
+  float* rv = has_running ? running_var.data_ptr<float>() : nullptr;
   launch_bn_finalize(sum.data_ptr<float>(), sumsq.data_ptr<float>(),
                      mean.data_ptr<float>(), rstd.data_ptr<float>(), rm, rv, M,
                      C, (float)eps, (float)momentum, stream());
@@ -303,9 +368,13 @@ std::vector<at::Tensor> bn_fwd_train(at::Tensor x, at::Tensor gamma,
 
 at::Tensor bn_fwd_eval(at::Tensor x, at::Tensor gamma, at::Tensor beta,
                        at::Tensor mean, at::Tensor rstd, bool relu) {
-  check_compute(x, "x");
-  int C = x.size(-1);
-  long long M = x.numel() / C;
+  const NormShape sh = norm_shape(x, "bn_fwd_eval", false);
+  const int C = sh.C;
+  const long long M = sh.R;
+  norm_check_vec(gamma, "gamma", x, at::kFloat, C, "bn_fwd_eval");
+  norm_check_vec(beta, "beta", x, at::kFloat, C, "bn_fwd_eval");
+  norm_check_vec(mean, "mean", x, at::kFloat, C, "bn_fwd_eval");
+  norm_check_vec(rstd, "rstd", x, at::kFloat, C, "bn_fwd_eval");
   auto y = at::empty_like(x);
   launch_bn_norm(is_bf16(x), relu, x.data_ptr(), nullptr,
                  mean.data_ptr<float>(), rstd.data_ptr<float>(), gamma.data_ptr<float>(),
@@ -316,10 +385,19 @@ at::Tensor bn_fwd_eval(at::Tensor x, at::Tensor gamma, at::Tensor beta,
 std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor y_post,
                                at::Tensor mean, at::Tensor rstd,
                                at::Tensor gamma, bool relu, bool want_dres) {
-  check_compute(x, "x");
-  check_compute(dy, "dy");
-  int C = x.size(-1);
-  long long M = x.numel() / C;
+  const NormShape sh = norm_shape(x, "bn_bwd", false);
+  const int C = sh.C;
+  const long long M = sh.R;
+  norm_check_like_x(dy, "dy", x, "bn_bwd");
+  if (relu) norm_check_like_x(y_post, "y_post", x, "bn_bwd");
+  norm_check_vec(mean, "mean", x, at::kFloat, C, "bn_bwd");
+  norm_check_vec(rstd, "rstd", x, at::kFloat, C, "bn_bwd");
+  norm_check_vec(gamma, "gamma", x, at::kFloat, C, "bn_bwd");
+  if (want_dres) {
+    const int velems = is_bf16(x) ? 8 : 4;
+    TORCH_CHECK(relu && (C % velems) == 0 && C <= 4096,
+                "bn dres needs the fused-relu vectorized path");
+  }
   auto sum_dy = at::zeros({C}, x.options().dtype(at::kFloat));
   auto sum_dyx = at::zeros({C}, x.options().dtype(at::kFloat));
   auto dx = at::empty_like(x);
@@ -328,9 +406,6 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor y_post,
   if (want_dres) {
     // fused y = relu(bn(x) + res) backward: dres = relu-masked dy, written
     // by the same dx pass. Needs the vectorized path (resnet channels).
-    const int velems = is_bf16(x) ? 8 : 4;
-    TORCH_CHECK(relu && (C % velems) == 0 && C <= 4096,
-                "bn dres needs the fused-relu vectorized path");
     dres = at::empty_like(x);
     dres_ptr = dres.data_ptr();
   }
@@ -895,10 +970,10 @@ at::Tensor softmax_bwd(at::Tensor y, at::Tensor dy, double scale) {
 // ---- llama ops -------------------------------------------------------------
 
 std::vector<at::Tensor> rms_fwd(at::Tensor x, at::Tensor w, double eps) {
-  check_compute(x, "x");
-  check_compute(w, "w");
-  int C = x.size(-1);
-  long long R = x.numel() / C;
+  const NormShape sh = norm_shape(x, "rms_fwd", false);
+  const int C = sh.C;
+  const long long R = sh.R;
+  norm_check_vec(w, "w", x, x.scalar_type(), C, "rms_fwd");
   auto y = at::empty_like(x);
   auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
   launch_rms_fwd(is_bf16(x), x.data_ptr(), nullptr, w.data_ptr(), y.data_ptr(),
@@ -910,11 +985,11 @@ std::vector<at::Tensor> rms_fwd(at::Tensor x, at::Tensor w, double eps) {
 // the residual stream and backward
 std::vector<at::Tensor> rms_add_fwd(at::Tensor x, at::Tensor res, at::Tensor w,
                                     double eps) {
-  check_compute(x, "x");
-  check_compute(res, "res");
-  TORCH_CHECK(x.sizes() == res.sizes() && x.scalar_type() == res.scalar_type());
-  int C = x.size(-1);
-  long long R = x.numel() / C;
+  const NormShape sh = norm_shape(x, "rms_add_fwd", false);
+  const int C = sh.C;
+  const long long R = sh.R;
+  norm_check_like_x(res, "res", x, "rms_add_fwd");
+  norm_check_vec(w, "w", x, x.scalar_type(), C, "rms_add_fwd");
   auto y = at::empty_like(x);
   auto z = at::empty_like(x);
   auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
@@ -926,10 +1001,12 @@ std::vector<at::Tensor> rms_add_fwd(at::Tensor x, at::Tensor res, at::Tensor w,
 
 std::vector<at::Tensor> rms_bwd(at::Tensor x, at::Tensor dy, at::Tensor w,
                                 at::Tensor rstd) {
-  check_compute(x, "x");
-  check_compute(dy, "dy");
-  int C = x.size(-1);
-  long long R = x.numel() / C;
+  const NormShape sh = norm_shape(x, "rms_bwd", false);
+  const int C = sh.C;
+  const long long R = sh.R;
+  norm_check_like_x(dy, "dy", x, "rms_bwd");
+  norm_check_vec(w, "w", x, x.scalar_type(), C, "rms_bwd");
+  norm_check_vec(rstd, "rstd", x, at::kFloat, R, "rms_bwd");
   auto dx = at::empty_like(x);
   auto dw = at::zeros({C}, x.options().dtype(at::kFloat));
   launch_rms_bwd(is_bf16(x), x.data_ptr(), dy.data_ptr(), w.data_ptr(),
@@ -940,11 +1017,13 @@ std::vector<at::Tensor> rms_bwd(at::Tensor x, at::Tensor dy, at::Tensor w,
 
 std::vector<at::Tensor> rms_bwd_plus(at::Tensor x, at::Tensor dy, at::Tensor w,
                                      at::Tensor rstd, at::Tensor plus) {
-  check_compute(x, "x");
-  check_compute(dy, "dy");
-  check_compute(plus, "plus");
-  int C = x.size(-1);
-  long long R = x.numel() / C;
+  const NormShape sh = norm_shape(x, "rms_bwd_plus", false);
+  const int C = sh.C;
+  const long long R = sh.R;
+  norm_check_like_x(dy, "dy", x, "rms_bwd_plus");
+  norm_check_like_x(plus, "plus", x, "rms_bwd_plus");
+  norm_check_vec(w, "w", x, x.scalar_type(), C, "rms_bwd_plus");
+  norm_check_vec(rstd, "rstd", x, at::kFloat, R, "rms_bwd_plus");
   auto dx = at::empty_like(x);
   auto dw = at::zeros({C}, x.options().dtype(at::kFloat));
   launch_rms_bwd(is_bf16(x), x.data_ptr(), dy.data_ptr(), w.data_ptr(),
@@ -957,11 +1036,14 @@ std::vector<at::Tensor> rms_bwd_plus(at::Tensor x, at::Tensor dy, at::Tensor w,
 std::vector<at::Tensor> ln_bwd_plus(at::Tensor x, at::Tensor dy, at::Tensor w,
                                     at::Tensor mean, at::Tensor rstd,
                                     at::Tensor plus) {
-  check_compute(x, "x");
-  check_compute(dy, "dy");
-  check_compute(plus, "plus");
-  int C = x.size(-1);
-  long long R = x.numel() / C;
+  const NormShape sh = norm_shape(x, "ln_bwd_plus", true);
+  const int C = sh.C;
+  const long long R = sh.R;
+  norm_check_like_x(dy, "dy", x, "ln_bwd_plus");
+  norm_check_like_x(plus, "plus", x, "ln_bwd_plus");
+  norm_check_vec(w, "w", x, x.scalar_type(), C, "ln_bwd_plus");
+  norm_check_vec(mean, "mean", x, at::kFloat, R, "ln_bwd_plus");
+  norm_check_vec(rstd, "rstd", x, at::kFloat, R, "ln_bwd_plus");
   auto dx = at::empty_like(x);
   auto dw = at::zeros({C}, x.options().dtype(at::kFloat));
   auto db = at::zeros({C}, x.options().dtype(at::kFloat));

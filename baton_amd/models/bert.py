@@ -46,12 +46,13 @@ class BertSelfAttention(nn.Module):
         self.qkv = BatonLinear(cfg.hidden, 3 * cfg.hidden)
         self.proj = BatonLinear(cfg.hidden, cfg.hidden)
 
-    def forward(self, x):
+    def forward(self, x, seq_lens=None):
         B, S, H = x.shape
         # packed QKV consumed as strided views — no permute copies on
         # either pass (AttnPackedFn writes dqkv slices in place)
         qkv = self.qkv(x).view(B, S, 3, self.heads, self.head_dim)
-        o = BF.attention_qkv(qkv, causal=False)              # [B, S, h, dh]
+        o = BF.attention_qkv(qkv, causal=False,
+                             seq_lens=seq_lens)              # [B, S, h, dh]
         return self.proj(o.reshape(B, S, H))
 
 
@@ -65,10 +66,10 @@ class BertLayer(nn.Module):
         self.fc2 = BatonLinear(cfg.ffn, cfg.hidden)
         self.ln2 = BatonLayerNorm(cfg.hidden, eps=cfg.layer_norm_eps)
 
-    def forward(self, x):
+    def forward(self, x, seq_lens=None):
         # post-LN, BERT style; residual adds fused into the LN kernels
         # (layer_norm_add: one pass writes z = x + sub(x) and normalizes it)
-        x = BF.layer_norm_add(self.attn(x), x, self.ln1.weight,
+        x = BF.layer_norm_add(self.attn(x, seq_lens), x, self.ln1.weight,
                               self.ln1.bias, self.ln1.eps)
         x = BF.layer_norm_add(self.fc2(self.act(self.fc1(x))), x,
                               self.ln2.weight, self.ln2.bias, self.ln2.eps)
@@ -77,7 +78,17 @@ class BertLayer(nn.Module):
 
 class BertForMaskedLM(nn.Module):
     """Encoder + MLM head. ``forward(input_ids)`` returns hidden states;
-    ``mlm_loss`` gathers the masked positions and applies the fused CE."""
+    ``mlm_loss`` gathers the masked positions and applies the fused CE.
+
+    Right-padded batches: ``forward(input_ids, seq_lens)`` with an int32 [B]
+    tensor of live lengths on the ids' device (``lengths_from_mask`` builds
+    and validates it from an attention mask). No live token then attends to
+    a pad token, so the hidden states at live positions do not depend on
+    what the padded positions hold; the hidden states at padded positions
+    are not meaningful and their labels must be -100. ``train_round(ids,
+    seq_lens, labels)`` trains on such data: LocalTrainer calls
+    ``model(ids, seq_lens)``. That path runs eagerly, since the captured
+    per-minibatch graph step takes a single input."""
 
     name = "bert-base-mlm"
 
@@ -96,13 +107,16 @@ class BertForMaskedLM(nn.Module):
         tc = train_config or TrainConfig(optimizer="adam", lr=5e-5)
         self._trainer = LocalTrainer(tc, loss_fn=self.mlm_loss)
 
-    def forward(self, input_ids: torch.Tensor) -> torch.Tensor:
+    def forward(self, input_ids: torch.Tensor,
+                seq_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, S = input_ids.shape
         pos = torch.arange(S, device=input_ids.device)
         x = self.tok_emb(input_ids) + self.pos_emb(pos)[None, :, :]
         x = self.emb_ln(x)
+        if seq_lens is not None:
+            seq_lens = seq_lens.to(torch.int32).contiguous()
         for layer in self.encoder:
-            x = layer(x)
+            x = layer(x, seq_lens)
         return x
 
     def mlm_logits(self, hidden: torch.Tensor, mask_positions: torch.Tensor):
@@ -139,14 +153,59 @@ def bert_tiny(train_config: Optional[TrainConfig] = None) -> BertForMaskedLM:
     return m
 
 
+PAD_ID = 1   # pad token of make_synthetic_mlm(var_len=True); 0 is [MASK]
+
+
+def lengths_from_mask(attention_mask: torch.Tensor) -> torch.Tensor:
+    """Host-side, data-preparation time: an attention mask [B, S] of ones
+    followed by zeros (right padding) -> int32 lengths [B] on the mask's
+    device, the form ``seq_lens`` takes everywhere below. This is where range
+    and right padding are validated (the kernels only clamp): raises
+    ValueError on values other than 0 / 1, on left padding and on holes."""
+    m = attention_mask
+    if m.dim() != 2:
+        raise ValueError(f"attention_mask must be [B, S], got {tuple(m.shape)}")
+    if m.dtype.is_floating_point or m.dtype == torch.bool:
+        vals = m.to(torch.float64)
+    else:
+        vals = m.to(torch.int64)
+    if not bool(((vals == 0) | (vals == 1)).all()):
+        raise ValueError("attention_mask may hold only 0 and 1")
+    live = vals != 0
+    lens = live.sum(dim=1)
+    S = m.shape[1]
+    expect = torch.arange(S, device=m.device)[None, :] < lens[:, None]
+    if not bool((live == expect).all()):
+        bad = (live != expect).any(dim=1).nonzero()[0].item()
+        raise ValueError(
+            f"attention_mask row {bad} is not ones followed by zeros: only "
+            "right padding can be expressed as a length")
+    return lens.to(torch.int32)
+
+
 def make_synthetic_mlm(
     n_samples: int, seq_len: int, vocab_size: int = 30522,
-    mask_frac: float = 0.15, seed: int = 0,
-) -> Tuple[torch.Tensor, torch.Tensor]:
+    mask_frac: float = 0.15, seed: int = 0, var_len: bool = False,
+):
     """Synthetic MLM data (no network for real corpora): random token ids;
     ~15% of positions masked (token replaced by id 0 = [MASK]); labels [n,S]
-    hold the original token there and -100 elsewhere (HF convention)."""
+    hold the original token there and -100 elsewhere (HF convention).
+
+    ``var_len=True`` returns ``(ids, seq_lens, labels)`` instead: lengths
+    drawn uniformly in [1, seq_len] (int32 [n]), live tokens in
+    [2, vocab_size), ``PAD_ID`` in the padded positions and -100 labels
+    there, and at least one masked live position per sample."""
     g = torch.Generator().manual_seed(seed)
+    if var_len:
+        ids = torch.randint(2, vocab_size, (n_samples, seq_len), generator=g)
+        lens = torch.randint(1, seq_len + 1, (n_samples,), generator=g)
+        live = torch.arange(seq_len)[None, :] < lens[:, None]
+        mask = (torch.rand(n_samples, seq_len, generator=g) < mask_frac) & live
+        mask[:, 0] |= ~mask.any(dim=1)   # position 0 is live in every sample
+        labels = torch.full_like(ids, -100)
+        labels[mask] = ids[mask]
+        masked_ids = ids.masked_fill(mask, 0).masked_fill(~live, PAD_ID)
+        return masked_ids, lens.to(torch.int32), labels
     ids = torch.randint(1, vocab_size, (n_samples, seq_len), generator=g)
     mask = torch.rand(n_samples, seq_len, generator=g) < mask_frac
     mask[:, 0] |= ~mask.any(dim=1)   # every sample has >= 1 masked position

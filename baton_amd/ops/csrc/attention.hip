@@ -8,20 +8,55 @@
 // Backward fuses the dsoftmax reduction: dx = scale * y * (dy - sum(dy*y)).
 #include "common.h"
 
-template <typename T, bool CAUSAL>
+// Per-sequence key lengths (right padding). The VARLEN instantiations take a
+// RowLens as their last argument: row r belongs to entry r / rows_per_len of
+// kv_len and has query position r % q_period. Its columns stop at
+// min(causal limit, L) with L = clamp(kv_len[entry], 0, C); a row whose query
+// position is >= L is stored as zeros without being read. The dense
+// instantiations take an empty struct and keep their code.
+struct NoLens {};
+struct RowLens {
+  const int* kv_len;
+  long long rows_per_len;
+  int q_period;
+};
+template <bool VARLEN> struct LenArg { using type = NoLens; };
+template <> struct LenArg<true> { using type = RowLens; };
+
+// last visible column of row r given its dense limit qpos; -1: a dead row
+DEVINL int len_limit(const RowLens& lens, long long r, int C, int qpos) {
+  const int L = min(max(lens.kv_len[r / lens.rows_per_len], 0), C);
+  return (int)(r % lens.q_period) >= L ? -1 : min(qpos, L - 1);
+}
+
+template <typename T, bool CAUSAL, bool VARLEN>
 __global__ void softmax_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
                                    long long R, int C, float scale,
-                                   int causal_seq) {
+                                   int causal_seq,
+                                   typename LenArg<VARLEN>::type lens) {
   __shared__ float scratch[kBlock / kWave];
   __shared__ float s_max;
   for (long long r = blockIdx.x; r < R; r += gridDim.x) {
     const T* row = x + r * C;
     T* yrow = y + r * C;
-    const int qpos = CAUSAL ? (int)(r % causal_seq) : C - 1;
+    int qpos = CAUSAL ? (int)(r % causal_seq) : C - 1;
     constexpr int V = VecTraits<T>::kElems;
     // vector path needs enough vectors to keep a wave busy: at C=128 it
     // left 16 of 256 threads active and measured SLOWER than scalar
     const bool vec = (C % V) == 0 && C >= V * 64;
+    if constexpr (VARLEN) {
+      qpos = len_limit(lens, r, C, qpos);
+      if (qpos < 0) {   // block-uniform: the whole block skips the barriers
+        if (vec) {
+          float f[V] = {};
+          for (int cv = threadIdx.x; cv < C / V; cv += blockDim.x)
+            vstore16(yrow + cv * V, f);
+        } else {
+          for (int c = threadIdx.x; c < C; c += blockDim.x) yrow[c] = (T)0.f;
+        }
+        continue;
+      }
+    }
     float m = -INFINITY;
     if (vec) {
       for (int cv = threadIdx.x; cv < C / V; cv += blockDim.x) {
@@ -131,10 +166,10 @@ __global__ void softmax_bwd_kernel(const T* __restrict__ y,
 // Wave-per-row softmax for short rows (C <= 1024): four independent
 // waves per block, wave-shuffle reductions, no block barriers — the
 // row-per-block form leaves most of a 256-thread block idle at S=128.
-template <typename T, bool CAUSAL>
+template <typename T, bool CAUSAL, bool VARLEN>
 __global__ __launch_bounds__(kBlock) void softmax_fwd_wave_kernel(
     const T* __restrict__ x, T* __restrict__ y, long long R, int C,
-    float scale, int causal_seq) {
+    float scale, int causal_seq, typename LenArg<VARLEN>::type lens) {
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   constexpr int V = VecTraits<T>::kElems;
@@ -143,7 +178,19 @@ __global__ __launch_bounds__(kBlock) void softmax_fwd_wave_kernel(
        r += (long long)gridDim.x * 4) {
     const T* row = x + r * C;
     T* yrow = y + r * C;
-    const int qpos = CAUSAL ? (int)(r % causal_seq) : C - 1;
+    int qpos = CAUSAL ? (int)(r % causal_seq) : C - 1;
+    if constexpr (VARLEN) {
+      qpos = len_limit(lens, r, C, qpos);
+      if (qpos < 0) {   // wave-uniform
+        if (vec) {
+          float f[V] = {};
+          for (int cv = lane; cv < C / V; cv += 64) vstore16(yrow + cv * V, f);
+        } else {
+          for (int c = lane; c < C; c += 64) yrow[c] = (T)0.f;
+        }
+        continue;
+      }
+    }
     float m = -INFINITY;
     if (vec) {
       for (int cv = lane; cv < C / V; cv += 64) {
@@ -235,10 +282,14 @@ __global__ __launch_bounds__(kBlock) void softmax_bwd_wave_kernel(
 }
 
 #define INST_SM_WAVE(T)                                                      \
-  template __global__ void softmax_fwd_wave_kernel<T, true>(                 \
-      const T*, T*, long long, int, float, int);                             \
-  template __global__ void softmax_fwd_wave_kernel<T, false>(                \
-      const T*, T*, long long, int, float, int);                             \
+  template __global__ void softmax_fwd_wave_kernel<T, true, false>(          \
+      const T*, T*, long long, int, float, int, NoLens);                     \
+  template __global__ void softmax_fwd_wave_kernel<T, false, false>(         \
+      const T*, T*, long long, int, float, int, NoLens);                     \
+  template __global__ void softmax_fwd_wave_kernel<T, true, true>(           \
+      const T*, T*, long long, int, float, int, RowLens);                    \
+  template __global__ void softmax_fwd_wave_kernel<T, false, true>(          \
+      const T*, T*, long long, int, float, int, RowLens);                    \
   template __global__ void softmax_bwd_wave_kernel<T>(const T*, const T*,    \
                                                       T*, long long, int,    \
                                                       float);
@@ -247,12 +298,14 @@ INST_SM_WAVE(float)
 INST_SM_WAVE(bf16)
 
 #define INST_SM(T)                                                           \
-  template __global__ void softmax_fwd_kernel<T, true>(const T*, T*,         \
-                                                       long long, int, float, \
-                                                       int);                 \
-  template __global__ void softmax_fwd_kernel<T, false>(const T*, T*,        \
-                                                        long long, int,      \
-                                                        float, int);         \
+  template __global__ void softmax_fwd_kernel<T, true, false>(               \
+      const T*, T*, long long, int, float, int, NoLens);                     \
+  template __global__ void softmax_fwd_kernel<T, false, false>(              \
+      const T*, T*, long long, int, float, int, NoLens);                     \
+  template __global__ void softmax_fwd_kernel<T, true, true>(                \
+      const T*, T*, long long, int, float, int, RowLens);                    \
+  template __global__ void softmax_fwd_kernel<T, false, true>(               \
+      const T*, T*, long long, int, float, int, RowLens);                    \
   template __global__ void softmax_bwd_kernel<T>(const T*, const T*, T*,     \
                                                  long long, int, float);
 
@@ -262,33 +315,40 @@ INST_SM(bf16)
 // ---- launchers -------------------------------------------------------------
 #include "launchers.h"
 
+// kv_len == nullptr launches the dense instantiations.
 void launch_softmax_fwd(bool is_bf16, const void* x, void* y, long long R,
-                        int C, float scale, int causal_seq, hipStream_t s) {
+                        int C, float scale, int causal_seq, const int* kv_len,
+                        long long rows_per_len, int q_period, hipStream_t s) {
+  const RowLens lens{kv_len, rows_per_len, q_period};
+  const bool causal = causal_seq > 0;
+#define SM_PICK(CALL, T)                                                     \
+  do {                                                                       \
+    if (kv_len) {                                                            \
+      if (causal) CALL(T, true, true, lens); else CALL(T, false, true, lens); \
+    } else {                                                                 \
+      if (causal) CALL(T, true, false, NoLens{});                            \
+      else CALL(T, false, false, NoLens{});                                  \
+    }                                                                        \
+  } while (0)
   if (C <= 1024) {   // wave-per-row: 4 rows/block, no block barriers
     const long long blocks = (R + 3) / 4;
     const int grid = blocks < kMaxGrid ? (int)blocks : kMaxGrid;
-    #define SMW_CALL(T, CZ)                                                   \
-      hipLaunchKernelGGL((softmax_fwd_wave_kernel<T, CZ>), dim3(grid),        \
+    #define SMW_CALL(T, CZ, VL, LENS)                                         \
+      hipLaunchKernelGGL((softmax_fwd_wave_kernel<T, CZ, VL>), dim3(grid),    \
                          dim3(kBlock), 0, s, (const T*)x, (T*)y, R, C, scale, \
-                         causal_seq)
-    if (is_bf16) {
-      if (causal_seq > 0) SMW_CALL(bf16, true); else SMW_CALL(bf16, false);
-    } else {
-      if (causal_seq > 0) SMW_CALL(float, true); else SMW_CALL(float, false);
-    }
+                         causal_seq, LENS)
+    if (is_bf16) SM_PICK(SMW_CALL, bf16); else SM_PICK(SMW_CALL, float);
     #undef SMW_CALL
     return;
   }
   const int grid = R < kMaxGrid ? (int)R : kMaxGrid;
-  #define SM_CALL(T, CZ)                                                     \
-    hipLaunchKernelGGL((softmax_fwd_kernel<T, CZ>), dim3(grid), dim3(kBlock), \
-                       0, s, (const T*)x, (T*)y, R, C, scale, causal_seq)
-  if (is_bf16) {
-    if (causal_seq > 0) SM_CALL(bf16, true); else SM_CALL(bf16, false);
-  } else {
-    if (causal_seq > 0) SM_CALL(float, true); else SM_CALL(float, false);
-  }
+  #define SM_CALL(T, CZ, VL, LENS)                                           \
+    hipLaunchKernelGGL((softmax_fwd_kernel<T, CZ, VL>), dim3(grid),          \
+                       dim3(kBlock), 0, s, (const T*)x, (T*)y, R, C, scale,  \
+                       causal_seq, LENS)
+  if (is_bf16) SM_PICK(SM_CALL, bf16); else SM_PICK(SM_CALL, float);
   #undef SM_CALL
+#undef SM_PICK
 }
 
 void launch_softmax_bwd(bool is_bf16, const void* y, const void* dy, void* dx,

@@ -9,6 +9,8 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <limits>
+
 #include "launchers.h"
 #include "wgrad_px_map.h"
 #include "dgrad_phase_map.h"
@@ -941,7 +943,27 @@ at::Tensor gemm_batched(at::Tensor A, at::Tensor B, int64_t layout,
   return C;
 }
 
-at::Tensor softmax_fwd(at::Tensor x, double scale, int64_t causal_seq) {
+// Per-sequence lengths of right-padded batches: an int32, contiguous tensor
+// of `count` elements on `like`'s device. The values stay on the device (the
+// kernels clamp them into range); only the tensor's metadata is checked.
+static const int* check_lens(const c10::optional<at::Tensor>& lens,
+                             const char* name, const at::Tensor& like,
+                             int64_t count, const char* count_name) {
+  if (!lens.has_value()) return nullptr;
+  const at::Tensor& t = *lens;
+  TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32, got ",
+              t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.device() == like.device(), name, " must be on ",
+              like.device(), " with the other arguments, got ", t.device());
+  TORCH_CHECK(t.numel() == count, name, " must have exactly ", count_name,
+              " = ", count, " elements, got ", t.numel());
+  return t.data_ptr<int>();
+}
+
+at::Tensor softmax_fwd(at::Tensor x, double scale, int64_t causal_seq,
+                       c10::optional<at::Tensor> kv_len, int64_t rows_per_len,
+                       int64_t q_period) {
   check_compute(x, "x");
   int C = x.size(-1);
   // the causal mask keeps columns c <= r % causal_seq of row r
@@ -949,9 +971,22 @@ at::Tensor softmax_fwd(at::Tensor x, double scale, int64_t causal_seq) {
               "softmax_fwd: causal_seq must be in [0, C = ", C, "], got ",
               causal_seq);
   long long R = x.numel() / C;
+  const int* lens = nullptr;
+  if (kv_len.has_value()) {
+    // row r has entry r / rows_per_len and query position r % q_period
+    TORCH_CHECK(rows_per_len > 0 && q_period > 0 &&
+                    q_period <= std::numeric_limits<int>::max(),
+                "softmax_fwd: kv_len needs rows_per_len > 0 and q_period > 0, "
+                "got ", rows_per_len, " and ", q_period);
+    TORCH_CHECK(R % rows_per_len == 0, "softmax_fwd: the row count ", R,
+                " is not a multiple of rows_per_len = ", rows_per_len);
+    lens = check_lens(kv_len, "kv_len", x, R / rows_per_len,
+                      "rows / rows_per_len");
+  }
   auto y = at::empty_like(x);
   launch_softmax_fwd(is_bf16(x), x.data_ptr(), y.data_ptr(), R, C,
-                     (float)scale, (int)causal_seq, stream());
+                     (float)scale, (int)causal_seq, lens,
+                     (long long)rows_per_len, (int)q_period, stream());
   return y;
 }
 
@@ -1140,7 +1175,8 @@ void strides3(const at::Tensor& t, long long* out) {
 }  // namespace
 
 std::vector<at::Tensor> flash_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                  at::Tensor o, bool causal) {
+                                  at::Tensor o, bool causal,
+                                  c10::optional<at::Tensor> seq_lens) {
   check_attn_view(q, "q", q);
   check_attn_view(k, "k", q);
   check_attn_view(v, "v", q);
@@ -1151,6 +1187,7 @@ std::vector<at::Tensor> flash_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   const int B = q.size(0), S = q.size(1), H = q.size(2), DH = q.size(3);
   const int KVH = k.size(2);
   const int G = H / KVH;
+  const int* lens = check_lens(seq_lens, "seq_lens", q, B, "B");
   auto lse = at::empty({(long long)B * H, S},
                        q.options().dtype(at::kFloat));
   long long qs[3], ks[3], vs[3], os[3];
@@ -1159,14 +1196,15 @@ std::vector<at::Tensor> flash_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   TORCH_CHECK(
       launch_flash_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                        lse.data_ptr<float>(), B, S, H, G, DH, scale, causal,
-                       qs, ks, vs, os, stream()),
+                       qs, ks, vs, os, lens, stream()),
       "flash_fwd: unsupported head_dim ", DH);
   return {o, lse};
 }
 
 void flash_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                at::Tensor dout, at::Tensor lse, at::Tensor dq, at::Tensor dk,
-               at::Tensor dv, bool causal) {
+               at::Tensor dv, bool causal,
+               c10::optional<at::Tensor> seq_lens) {
   check_attn_view(q, "q", q);
   check_attn_view(k, "k", q);
   check_attn_view(v, "v", q);
@@ -1193,31 +1231,37 @@ void flash_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                   lse.size(1) == S,
               "lse must be [B*H, S] = [", (int64_t)B * H, ", ", S, "], got ",
               lse.sizes());
+  const int* lens = check_lens(seq_lens, "seq_lens", q, B, "B");
   auto delta = at::empty_like(lse);
   long long qs[3], ks[3], vs[3], os[3], dos[3], dqs[3], dks[3], dvs[3];
   strides3(q, qs); strides3(k, ks); strides3(v, vs); strides3(o, os);
   strides3(dout, dos); strides3(dq, dqs); strides3(dk, dks); strides3(dv, dvs);
   const float scale = 1.0f / std::sqrt((float)DH);
   launch_flash_delta(dout.data_ptr(), o.data_ptr(), delta.data_ptr<float>(),
-                     B, S, H, DH, dos, os, stream());
+                     B, S, H, DH, dos, os, lens, stream());
   TORCH_CHECK(
       launch_flash_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                           dout.data_ptr(), lse.data_ptr<float>(),
                           delta.data_ptr<float>(), dq.data_ptr(), B, S, H, G,
-                          DH, scale, causal, qs, ks, vs, dos, dqs, stream()),
+                          DH, scale, causal, qs, ks, vs, dos, dqs, lens,
+                          stream()),
       "flash_bwd_dq: unsupported head_dim ", DH);
   TORCH_CHECK(
       launch_flash_bwd_dkv(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                            dout.data_ptr(), lse.data_ptr<float>(),
                            delta.data_ptr<float>(), dk.data_ptr(),
                            dv.data_ptr(), B, S, H, G, DH, scale, causal, qs,
-                           ks, vs, dos, dks, dvs, stream()),
+                           ks, vs, dos, dks, dvs, lens, stream()),
       "flash_bwd_dkv: unsupported head_dim ", DH);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.def("flash_fwd", &flash_fwd);
-  m.def("flash_bwd", &flash_bwd);
+  m.def("flash_fwd", &flash_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("o"), py::arg("causal"), py::arg("seq_lens") = py::none());
+  m.def("flash_bwd", &flash_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("dq"),
+        py::arg("dk"), py::arg("dv"), py::arg("causal"),
+        py::arg("seq_lens") = py::none());
   m.def("rms_add_fwd", &rms_add_fwd);
   m.def("rms_bwd_plus", &rms_bwd_plus);
   m.def("sgd_step", &sgd_step, "fused SGD step", py::arg("p"), py::arg("g"),
@@ -1277,7 +1321,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("layout"), py::arg("out_f32") = false, py::arg("alpha") = 1.0,
         py::arg("b_group") = 1);
   m.def("softmax_fwd", &softmax_fwd, py::arg("x"), py::arg("scale") = 1.0,
-        py::arg("causal_seq") = 0);
+        py::arg("causal_seq") = 0, py::arg("kv_len") = py::none(),
+        py::arg("rows_per_len") = 0, py::arg("q_period") = 0);
   m.def("softmax_bwd", &softmax_bwd);
   m.def("rms_fwd", &rms_fwd);
   m.def("rms_bwd", &rms_bwd);

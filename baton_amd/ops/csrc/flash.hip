@@ -76,11 +76,42 @@ DEVINL s16x8 lds128(const bf16* p) {
              s16x8*>((const __attribute__((address_space(3))) bf16*)p);
 }
 
+// ---- per-sequence lengths ---------------------------------------------------
+//
+// VARLEN instantiations take seq_lens (int32 [B], right padding: the live
+// tokens of batch element b are rows 0 .. L_b - 1) as their last argument and
+// run "the same kernel at S = L_b": L replaces S in every row guard, key mask
+// and loop bound, so the live rows walk the same tiles in the same order as
+// the dense kernel on the [:L_b] slices and are bit-identical to it. Rows
+// L_b .. S-1 of every output are stored as +0; nothing is read from them.
+// The dense instantiations take an empty struct instead and keep their code.
+struct NoLens {};
+template <bool VARLEN> struct LenArg { using type = NoLens; };
+template <> struct LenArg<true> { using type = const int*; };
+
+// block-uniform (b comes from blockIdx): stays in an SGPR. Clamped into
+// [0, S] so a bad length cannot move an access out of bounds.
+template <bool VARLEN>
+DEVINL int live_len(typename LenArg<VARLEN>::type lens, int b, int S) {
+  if constexpr (VARLEN) return min(max(lens[b], 0), S);
+  else return S;
+}
+
+// one lane's share of a [.., DH] output row (the epilogues' store pattern)
+template <int DH>
+DEVINL void store_zero_row(bf16* row, int hi) {
+#pragma unroll
+  for (int db = 0; db < DH / 32; ++db)
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd)
+      *reinterpret_cast<u32x2*>(&row[db * 32 + qd * 8 + hi * 4]) = u32x2{0u, 0u};
+}
+
 // ---- forward ---------------------------------------------------------------
 //
 // grid: (ceil(S/QB), B*H). q/k/v strided [B,S,(kv)h,DH]; o [B,S,H,DH]
 // (d contiguous); lse [B*H, S] fp32 = m + log(l).
-template <int DH, bool CAUSAL>
+template <int DH, bool CAUSAL, bool VARLEN>
 __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, bf16* __restrict__ O,
@@ -88,7 +119,8 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
     long long sqB, long long sqS, long long sqH,
     long long skB, long long skS, long long skH,
     long long svB, long long svS, long long svH,
-    long long soB, long long soS, long long soH) {
+    long long soB, long long soS, long long soH,
+    typename LenArg<VARLEN>::type lens) {
   constexpr int F = DH / 16;        // QK^T mfma count per 32-kv subtile
   constexpr int DB = DH / 32;       // O^T 32-row blocks
   constexpr int NCK = DH / 32;      // 16-B staging chunks per thread/operand
@@ -116,8 +148,17 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
 
   const int q0 = qblk * QB;
   const int qg = q0 + wid * QW + lq;          // this lane's q row
-  const bool qvalid = qg < S;
-  const int qmax_w = min(q0 + wid * QW + QW - 1, S - 1);
+  const int L = live_len<VARLEN>(lens, b, S);
+  if (VARLEN && q0 >= L) {
+    // dead block (taken by the whole block, before any barrier): no loads
+    if (qg < S) {
+      if (lane < 32) LSE[(long long)bh * S + qg] = 0.f;
+      store_zero_row<DH>(Op + (long long)qg * soS, hi);
+    }
+    return;
+  }
+  const bool qvalid = qg < L;
+  const int qmax_w = min(q0 + wid * QW + QW - 1, L - 1);
 
   // Q^T B-fragments: lane holds Q[qg][f*16 + hi*8 .. +7]
   s16x8 qf[F];
@@ -134,7 +175,7 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
   float m_run = -INFINITY;
   float l_run = 0.f;
 
-  const int nkv_block = CAUSAL ? min(S, q0 + QB) : S;
+  const int nkv_block = CAUSAL ? min(L, q0 + QB) : L;
   const int ntile = (nkv_block + KVB - 1) / KVB;
 
   // ---- staging helpers (register-staged; T14 split) ----
@@ -147,7 +188,7 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
       const int kv = idx / (DH / 8);
       const int slot = idx % (DH / 8);
       const int kvg = k0 + kv;
-      if (kvg < S) {
+      if (kvg < L) {
         kreg[c] = *reinterpret_cast<const s16x8*>(
             &Kp[(long long)kvg * skS + slot * 8]);
         vreg[c] = *reinterpret_cast<const s16x8*>(
@@ -203,8 +244,8 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
         const int kvl = (r & 3) + 8 * (r >> 2) + 4 * hi;
         const int kv_g0 = k0 + kvl;
         const int kv_g1 = k0 + 32 + kvl;
-        const bool v0 = kv_g0 < S && (!CAUSAL || kv_g0 <= qg);
-        const bool v1 = kv_g1 < S && (!CAUSAL || kv_g1 <= qg);
+        const bool v0 = kv_g0 < L && (!CAUSAL || kv_g0 <= qg);
+        const bool v1 = kv_g1 < L && (!CAUSAL || kv_g1 <= qg);
         p0[r] = v0 ? sa0[r] * scale : -1e30f;
         p1[r] = v1 ? sa1[r] * scale : -1e30f;
         tm = fmaxf(tm, fmaxf(p0[r], p1[r]));
@@ -272,7 +313,13 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
     }
   }
 
-  if (!qvalid) return;
+  if (!qvalid) {
+    if (VARLEN && qg < S) {       // padded row of a live block
+      if (lane < 32) LSE[(long long)bh * S + qg] = 0.f;
+      store_zero_row<DH>(Op + (long long)qg * soS, hi);
+    }
+    return;
+  }
   const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
   if (lane < 32) LSE[(long long)bh * S + qg] = m_run + __logf(fmaxf(l_run, 1e-30f));
   bf16* orow = Op + (long long)qg * soS;
@@ -294,18 +341,21 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
 // delta[bh, q] = rowsum(dO o O) — one wave per row, vectorized 16-B loads.
 // grid: (ceil(S/4), B*H); one wave per (bh, q) row. DH is a multiple of 8,
 // so lanes 0..DH/8-1 each reduce one 16-B chunk.
-template <int DH>
+template <int DH, bool VARLEN>
 __global__ __launch_bounds__(256) void flash_delta_kernel(
     const bf16* __restrict__ dO, const bf16* __restrict__ O,
     float* __restrict__ DELTA, int S, int H,
     long long doB, long long doS, long long doH,
-    long long oB, long long oS, long long oH) {
+    long long oB, long long oS, long long oH,
+    typename LenArg<VARLEN>::type lens) {
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   const int q = blockIdx.x * 4 + wid;
   if (q >= S) return;
   const int bh = blockIdx.y;
   const int b = bh / H, h = bh % H;
+  // padded rows are not read; dq and dk/dv never consume their delta
+  if (VARLEN && q >= live_len<VARLEN>(lens, b, S)) return;
   const bf16* dop = dO + b * doB + h * doH + (long long)q * doS;
   const bf16* op = O + b * oB + h * oH + (long long)q * oS;
   float acc = 0.f;
@@ -324,7 +374,7 @@ __global__ __launch_bounds__(256) void flash_delta_kernel(
 // dQ kernel: q-tile-major (same block geometry as forward). Per kv tile:
 // recompute P^T from lse, dP^T = mfma(V, dO^T), dS^T, then
 // dQ^T += mfma(K^T, dS^T-frags). No atomics: dQ accumulates in registers.
-template <int DH, bool CAUSAL>
+template <int DH, bool CAUSAL, bool VARLEN>
 __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, const bf16* __restrict__ dO,
@@ -334,7 +384,8 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
     long long skB, long long skS, long long skH,
     long long svB, long long svS, long long svH,
     long long doB, long long doS, long long doH,
-    long long dqB, long long dqS, long long dqH) {
+    long long dqB, long long dqS, long long dqH,
+    typename LenArg<VARLEN>::type lens) {
   constexpr int F = DH / 16;
   constexpr int DB = DH / 32;
   constexpr int NCK = DH / 32;
@@ -362,8 +413,13 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
 
   const int q0 = blockIdx.x * QB;
   const int qg = q0 + wid * QW + lq;
-  const bool qvalid = qg < S;
-  const int qmax_w = min(q0 + wid * QW + QW - 1, S - 1);
+  const int L = live_len<VARLEN>(lens, b, S);
+  if (VARLEN && q0 >= L) {        // dead block: whole block, before any barrier
+    if (qg < S) store_zero_row<DH>(dQp + (long long)qg * dqS, hi);
+    return;
+  }
+  const bool qvalid = qg < L;
+  const int qmax_w = min(q0 + wid * QW + QW - 1, L - 1);
 
   s16x8 qf[F], dof[F];
 #pragma unroll
@@ -383,7 +439,7 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
 
   f32x16 dq_acc[DB] = {};
 
-  const int nkv_block = CAUSAL ? min(S, q0 + QB) : S;
+  const int nkv_block = CAUSAL ? min(L, q0 + QB) : L;
   const int ntile = (nkv_block + KVB - 1) / KVB;
 
   for (int t = 0; t < ntile; ++t) {
@@ -397,7 +453,7 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
       const int slot = idx % (DH / 8);
       const int kvg = k0 + kv;
       s16x8 kr = s16x8{}, vr = s16x8{};
-      if (kvg < S) {
+      if (kvg < L) {
         kr = *reinterpret_cast<const s16x8*>(
             &Kp[(long long)kvg * skS + slot * 8]);
         vr = *reinterpret_cast<const s16x8*>(
@@ -431,7 +487,7 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int kv_g = k0 + st * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        const bool vld = kv_g < S && (!CAUSAL || kv_g <= qg);
+        const bool vld = kv_g < L && (!CAUSAL || kv_g <= qg);
         const float p = vld ? __expf(sacc[r] * scale - lse_q) : 0.f;
         ds[r] = p * (dpacc[r] - delta_q) * scale;
       }
@@ -468,7 +524,10 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
         }
   }
 
-  if (!qvalid) return;
+  if (!qvalid) {
+    if (VARLEN && qg < S) store_zero_row<DH>(dQp + (long long)qg * dqS, hi);
+    return;
+  }
   bf16* dqrow = dQp + (long long)qg * dqS;
 #pragma unroll
   for (int db = 0; db < DB; ++db)
@@ -490,7 +549,7 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
 // Outputs are PER-Q-HEAD (GQA callers group-sum), so no atomics.
 constexpr int KVBB = 128;           // kv rows per block (32 per wave)
 
-template <int DH, bool CAUSAL>
+template <int DH, bool CAUSAL, bool VARLEN>
 __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, const bf16* __restrict__ dO,
@@ -502,7 +561,8 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
     long long svB, long long svS, long long svH,
     long long doB, long long doS, long long doH,
     long long dkB, long long dkS, long long dkH,
-    long long dvB, long long dvS, long long dvH) {
+    long long dvB, long long dvS, long long dvH,
+    typename LenArg<VARLEN>::type lens) {
   constexpr int F = DH / 16;
   constexpr int DB = DH / 32;
 
@@ -535,7 +595,15 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
   const int kv0 = blockIdx.x * KVBB;
   const int kv_w = kv0 + wid * 32;            // wave's kv base
   const int kvg = kv_w + lkv;                 // lane's kv row
-  const bool kvalid = kvg < S;
+  const int L = live_len<VARLEN>(lens, b, S);
+  if (VARLEN && kv0 >= L) {       // dead block: whole block, before staging
+    if (kvg < S) {
+      store_zero_row<DH>(dKp + (long long)kvg * dkS, hi);
+      store_zero_row<DH>(dVp + (long long)kvg * dvS, hi);
+    }
+    return;
+  }
+  const bool kvalid = kvg < L;
 
   // ---- stage block-persistent K/V row images (swizzled)
   {
@@ -545,7 +613,7 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
       const int slot = idx % (DH / 8);
       const int g = kv0 + kv;
       s16x8 kr = s16x8{}, vr = s16x8{};
-      if (g < S) {
+      if (g < L) {
         kr = *reinterpret_cast<const s16x8*>(
             &Kp[(long long)g * skS + slot * 8]);
         vr = *reinterpret_cast<const s16x8*>(
@@ -561,7 +629,7 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
   f32x16 dv_acc[DB] = {}, dk_acc[DB] = {};
 
   const int qt0 = CAUSAL ? (kv0 / 32) : 0;    // first q tile that can see kv0
-  const int nqt = (S + 31) / 32;
+  const int nqt = (L + 31) / 32;
 
   for (int qt = qt0; qt < nqt; ++qt) {
     const int q0t = qt * 32;
@@ -574,7 +642,7 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
         const int slot = idx % (DH / 8);
         const int g = q0t + qr;
         s16x8 qr16 = s16x8{}, dor16 = s16x8{};
-        if (g < S) {
+        if (g < L) {
           qr16 = *reinterpret_cast<const s16x8*>(
               &Qp[(long long)g * sqS + slot * 8]);
           dor16 = *reinterpret_cast<const s16x8*>(
@@ -613,7 +681,7 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int q_g = q0t + (r & 3) + 8 * (r >> 2) + 4 * hi;
-      const bool vld = q_g < S && kvalid && (!CAUSAL || kvg <= q_g);
+      const bool vld = q_g < L && kvalid && (!CAUSAL || kvg <= q_g);
       float lse_r = 0.f, del_r = 0.f;
       if (vld) {
         lse_r = LSE[(long long)bh * S + q_g];
@@ -676,7 +744,13 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
       }
   }
 
-  if (!kvalid) return;
+  if (!kvalid) {
+    if (VARLEN && kvg < S) {      // padded row of a live block
+      store_zero_row<DH>(dKp + (long long)kvg * dkS, hi);
+      store_zero_row<DH>(dVp + (long long)kvg * dvS, hi);
+    }
+    return;
+  }
   bf16* dkrow = dKp + (long long)kvg * dkS;
   bf16* dvrow = dVp + (long long)kvg * dvS;
 #pragma unroll
@@ -701,23 +775,36 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
 
 #include "launchers.h"
 
+// seq_lens == nullptr launches the dense instantiations (empty-struct last
+// argument); otherwise the VARLEN ones on the same grid.
 bool launch_flash_fwd(const void* Q, const void* K, const void* V, void* O,
                       float* LSE, int B, int S, int H, int G, int DH,
                       float scale, bool causal,
                       const long long* qs, const long long* ks,
                       const long long* vs, const long long* os,
-                      hipStream_t s) {
+                      const int* seq_lens, hipStream_t s) {
   if (DH != 32 && DH != 64 && DH != 128) return false;
   dim3 grid((S + fa::QB - 1) / fa::QB, B * H);
-#define FA_CALL(DHV, CZ)                                                      \
-  hipLaunchKernelGGL((fa::flash_fwd_kernel<DHV, CZ>), grid,                   \
+#define FA_CALL(DHV, CZ, VL, LENS)                                            \
+  hipLaunchKernelGGL((fa::flash_fwd_kernel<DHV, CZ, VL>), grid,               \
                      dim3(fa::THREADS), 0, s, (const bf16*)Q, (const bf16*)K, \
                      (const bf16*)V, (bf16*)O, LSE, S, H, G, scale,           \
                      qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],                \
-                     vs[0], vs[1], vs[2], os[0], os[1], os[2])
-  if (DH == 32) { if (causal) FA_CALL(32, true); else FA_CALL(32, false); }
-  else if (DH == 64) { if (causal) FA_CALL(64, true); else FA_CALL(64, false); }
-  else { if (causal) FA_CALL(128, true); else FA_CALL(128, false); }
+                     vs[0], vs[1], vs[2], os[0], os[1], os[2], LENS)
+#define FA_DH(DHV)                                                            \
+  do {                                                                        \
+    if (seq_lens) {                                                           \
+      if (causal) FA_CALL(DHV, true, true, seq_lens);                         \
+      else FA_CALL(DHV, false, true, seq_lens);                               \
+    } else {                                                                  \
+      if (causal) FA_CALL(DHV, true, false, fa::NoLens{});                    \
+      else FA_CALL(DHV, false, false, fa::NoLens{});                          \
+    }                                                                         \
+  } while (0)
+  if (DH == 32) FA_DH(32);
+  else if (DH == 64) FA_DH(64);
+  else FA_DH(128);
+#undef FA_DH
 #undef FA_CALL
   return true;
 }
@@ -725,15 +812,21 @@ bool launch_flash_fwd(const void* Q, const void* K, const void* V, void* O,
 void launch_flash_delta(const void* dO, const void* O, float* delta,
                         int B, int S, int H, int DH,
                         const long long* dos, const long long* os,
-                        hipStream_t s) {
+                        const int* seq_lens, hipStream_t s) {
   dim3 grid((S + 3) / 4, B * H);
-#define FD_CALL(DHV)                                                         \
-  hipLaunchKernelGGL((fa::flash_delta_kernel<DHV>), grid, dim3(256), 0, s,   \
-                     (const bf16*)dO, (const bf16*)O, delta, S, H,           \
-                     dos[0], dos[1], dos[2], os[0], os[1], os[2])
-  if (DH == 32) FD_CALL(32);
-  else if (DH == 64) FD_CALL(64);
-  else FD_CALL(128);
+#define FD_CALL(DHV, VL, LENS)                                               \
+  hipLaunchKernelGGL((fa::flash_delta_kernel<DHV, VL>), grid, dim3(256), 0,  \
+                     s, (const bf16*)dO, (const bf16*)O, delta, S, H,        \
+                     dos[0], dos[1], dos[2], os[0], os[1], os[2], LENS)
+#define FD_DH(DHV)                                                           \
+  do {                                                                       \
+    if (seq_lens) FD_CALL(DHV, true, seq_lens);                              \
+    else FD_CALL(DHV, false, fa::NoLens{});                                  \
+  } while (0)
+  if (DH == 32) FD_DH(32);
+  else if (DH == 64) FD_DH(64);
+  else FD_DH(128);
+#undef FD_DH
 #undef FD_CALL
 }
 
@@ -743,19 +836,31 @@ bool launch_flash_bwd_dq(const void* Q, const void* K, const void* V,
                          float scale, bool causal,
                          const long long* qs, const long long* ks,
                          const long long* vs, const long long* dos,
-                         const long long* dqs, hipStream_t s) {
+                         const long long* dqs, const int* seq_lens,
+                         hipStream_t s) {
   if (DH != 32 && DH != 64 && DH != 128) return false;
   dim3 grid((S + fa::QB - 1) / fa::QB, B * H);
-#define DQ_CALL(DHV, CZ)                                                      \
-  hipLaunchKernelGGL((fa::flash_bwd_dq_kernel<DHV, CZ>), grid,                \
+#define DQ_CALL(DHV, CZ, VL, LENS)                                            \
+  hipLaunchKernelGGL((fa::flash_bwd_dq_kernel<DHV, CZ, VL>), grid,            \
                      dim3(fa::THREADS), 0, s, (const bf16*)Q, (const bf16*)K, \
                      (const bf16*)V, (const bf16*)dO, LSE, DELTA, (bf16*)dQ,  \
                      S, H, G, scale, qs[0], qs[1], qs[2], ks[0], ks[1],       \
                      ks[2], vs[0], vs[1], vs[2], dos[0], dos[1], dos[2],      \
-                     dqs[0], dqs[1], dqs[2])
-  if (DH == 32) { if (causal) DQ_CALL(32, true); else DQ_CALL(32, false); }
-  else if (DH == 64) { if (causal) DQ_CALL(64, true); else DQ_CALL(64, false); }
-  else { if (causal) DQ_CALL(128, true); else DQ_CALL(128, false); }
+                     dqs[0], dqs[1], dqs[2], LENS)
+#define DQ_DH(DHV)                                                            \
+  do {                                                                        \
+    if (seq_lens) {                                                           \
+      if (causal) DQ_CALL(DHV, true, true, seq_lens);                         \
+      else DQ_CALL(DHV, false, true, seq_lens);                               \
+    } else {                                                                  \
+      if (causal) DQ_CALL(DHV, true, false, fa::NoLens{});                    \
+      else DQ_CALL(DHV, false, false, fa::NoLens{});                          \
+    }                                                                         \
+  } while (0)
+  if (DH == 32) DQ_DH(32);
+  else if (DH == 64) DQ_DH(64);
+  else DQ_DH(128);
+#undef DQ_DH
 #undef DQ_CALL
   return true;
 }
@@ -767,19 +872,31 @@ bool launch_flash_bwd_dkv(const void* Q, const void* K, const void* V,
                           const long long* qs, const long long* ks,
                           const long long* vs, const long long* dos,
                           const long long* dks, const long long* dvs,
-                          hipStream_t s) {
+                          const int* seq_lens, hipStream_t s) {
   if (DH != 32 && DH != 64 && DH != 128) return false;
   dim3 grid((S + fa::KVBB - 1) / fa::KVBB, B * H);
-#define DKV_CALL(DHV, CZ)                                                     \
-  hipLaunchKernelGGL((fa::flash_bwd_dkv_kernel<DHV, CZ>), grid,               \
+#define DKV_CALL(DHV, CZ, VL, LENS)                                           \
+  hipLaunchKernelGGL((fa::flash_bwd_dkv_kernel<DHV, CZ, VL>), grid,           \
                      dim3(fa::THREADS), 0, s, (const bf16*)Q, (const bf16*)K, \
                      (const bf16*)V, (const bf16*)dO, LSE, DELTA, (bf16*)dK,  \
                      (bf16*)dV, S, H, G, scale, qs[0], qs[1], qs[2], ks[0],   \
                      ks[1], ks[2], vs[0], vs[1], vs[2], dos[0], dos[1],       \
-                     dos[2], dks[0], dks[1], dks[2], dvs[0], dvs[1], dvs[2])
-  if (DH == 32) { if (causal) DKV_CALL(32, true); else DKV_CALL(32, false); }
-  else if (DH == 64) { if (causal) DKV_CALL(64, true); else DKV_CALL(64, false); }
-  else { if (causal) DKV_CALL(128, true); else DKV_CALL(128, false); }
+                     dos[2], dks[0], dks[1], dks[2], dvs[0], dvs[1], dvs[2],  \
+                     LENS)
+#define DKV_DH(DHV)                                                           \
+  do {                                                                        \
+    if (seq_lens) {                                                           \
+      if (causal) DKV_CALL(DHV, true, true, seq_lens);                        \
+      else DKV_CALL(DHV, false, true, seq_lens);                              \
+    } else {                                                                  \
+      if (causal) DKV_CALL(DHV, true, false, fa::NoLens{});                   \
+      else DKV_CALL(DHV, false, false, fa::NoLens{});                         \
+    }                                                                         \
+  } while (0)
+  if (DH == 32) DKV_DH(32);
+  else if (DH == 64) DKV_DH(64);
+  else DKV_DH(128);
+#undef DKV_DH
 #undef DKV_CALL
   return true;
 }

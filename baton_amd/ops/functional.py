@@ -698,22 +698,37 @@ def batched_matmul(A, B, layout: int, alpha: float = 1.0, b_group: int = 1):
 
 
 class SoftmaxFn(torch.autograd.Function):
-    """y = softmax(scale * x [+ causal mask]) over the last dim."""
+    """y = softmax(scale * x [+ causal mask] [+ key lengths]) over the last
+    dim. With ``kv_len`` (int32, one entry per ``rows_per_len`` consecutive
+    rows; a row's query position is ``r % q_period``) the columns of a row
+    stop at its entry's length L, and a row whose query position is >= L is
+    all zeros. The backward needs no lengths: y == 0 gives dx == 0."""
 
     @staticmethod
-    def forward(ctx, x, scale: float, causal_seq: int = 0):
+    def forward(ctx, x, scale: float, causal_seq: int = 0, kv_len=None,
+                rows_per_len: int = 0, q_period: int = 0):
         x = x.contiguous()
         if _on_gpu(x):
-            y = require_hip().softmax_fwd(x, scale, causal_seq)
+            y = require_hip().softmax_fwd(x, scale, causal_seq, kv_len,
+                                          rows_per_len, q_period)
         else:
-            z = x.float() * scale
+            C = x.shape[-1]
+            z = (x.float() * scale).reshape(-1, C)
+            cols = torch.arange(C)[None, :]
             if causal_seq > 0:
-                S = causal_seq
-                C = x.shape[-1]
-                q = torch.arange(z.numel() // C) % S
-                mask = torch.arange(C)[None, :] > q[:, None]
-                z = z.reshape(-1, C).masked_fill(mask, float("-inf")).reshape(x.shape)
-            y = torch.softmax(z, dim=-1).to(x.dtype)
+                q = torch.arange(z.shape[0]) % causal_seq
+                z = z.masked_fill(cols > q[:, None], float("-inf"))
+            dead = None
+            if kv_len is not None:
+                rows = torch.arange(z.shape[0])
+                L = kv_len.long().clamp(0, C)[rows // rows_per_len]
+                dead = (rows % q_period >= L)[:, None]
+                # a dead row keeps its scores (an all -inf row has no softmax)
+                z = z.masked_fill((cols >= L[:, None]) & ~dead, float("-inf"))
+            y = torch.softmax(z, dim=-1)
+            if dead is not None:
+                y = y.masked_fill(dead, 0.0)
+            y = y.reshape(x.shape).to(x.dtype)
         ctx.save_for_backward(y)
         ctx.scale = scale
         return y
@@ -722,35 +737,50 @@ class SoftmaxFn(torch.autograd.Function):
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
         dy = dy.contiguous()
+        rest = (None,) * 5
         if _on_gpu(dy):
-            return require_hip().softmax_bwd(y, dy, ctx.scale), None, None
+            return (require_hip().softmax_bwd(y, dy, ctx.scale),) + rest
         yf = y.float()
         dyf = dy.float()
         dot = (yf * dyf).sum(-1, keepdim=True)
-        return (ctx.scale * yf * (dyf - dot)).to(y.dtype), None, None
+        return ((ctx.scale * yf * (dyf - dot)).to(y.dtype),) + rest
 
 
-def softmax(x, scale: float = 1.0, causal_seq: int = 0):
-    return SoftmaxFn.apply(x, scale, causal_seq)
+def softmax(x, scale: float = 1.0, causal_seq: int = 0, kv_len=None,
+            rows_per_len: int = 0, q_period: int = 0):
+    return SoftmaxFn.apply(x, scale, causal_seq, kv_len, rows_per_len,
+                           q_period)
 
 
-def attention(q, k, v, causal: bool = False):
+def attention(q, k, v, causal: bool = False, seq_lens=None, heads: int = 1):
     """Multi-head attention core on batched MFMA GEMMs + fused softmax.
     q: [nb, S, Dh] (nb = B*H); k, v: [nb, S, Dh] or [nb/g, S, Dh] (GQA —
-    the shared KV heads are indexed in-kernel, never copied)."""
+    the shared KV heads are indexed in-kernel, never copied).
+
+    ``seq_lens`` (int32 [B], on q's device) marks right-padded batches:
+    ``heads`` consecutive entries of q's leading dim share one length L_b,
+    key j is visible to query i iff j < L_b (and j <= i if causal), and rows
+    i >= L_b of the output and of every gradient are exactly 0. This path
+    still multiplies the padded rows of k, v and the incoming gradient by
+    exact zeros, so they must be finite (the fused flash path never reads
+    them)."""
     import math
 
     S, Dh = q.shape[-2], q.shape[-1]
     g = q.shape[0] // k.shape[0]
     scores = batched_matmul(q, k, 0, 1.0, g)              # [nb, S, S]
-    probs = softmax(scores, 1.0 / math.sqrt(Dh), S if causal else 0)
+    probs = softmax(scores, 1.0 / math.sqrt(Dh), S if causal else 0,
+                    seq_lens, heads * S, S)
     return batched_matmul(probs, v, 1, 1.0, g)            # [nb, S, Dh]
 
 
-def _attn_core_fwd(ops, q, k, v, causal):
+def _attn_core_fwd(ops, q, k, v, causal, seq_lens=None):
     """q/k/v: [B,S,h|kvh,dh] strided VIEWS — consumed in place by the
     strided batched GEMM (no permute copies). Returns (o [B,S,h,dh]
-    contiguous-in-that-layout, probs [B*h,S,S])."""
+    contiguous-in-that-layout, probs [B*h,S,S]). With ``seq_lens`` the
+    softmax zeroes the masked columns and the dead rows of probs; the GEMMs
+    around it (and the whole backward) then produce exact zeros in the padded
+    rows as long as the padded rows of k, v and dout are finite."""
     import math
 
     B, S, h, dh = q.shape
@@ -761,7 +791,8 @@ def _attn_core_fwd(ops, q, k, v, causal):
         q, k, None, layout=0, M=S, N=S, K=dh, nbatch=nb, heads=h, b_group=g,
         alpha=1.0, saO=q.stride(0), saI=q.stride(2), lda=q.stride(1),
         sbO=k.stride(0), sbI=k.stride(2), ldb=k.stride(1))
-    probs = ops.softmax_fwd(scores, 1.0 / math.sqrt(dh), S if causal else 0)
+    probs = ops.softmax_fwd(scores, 1.0 / math.sqrt(dh), S if causal else 0,
+                            seq_lens, h * S, S)
     o = torch.empty(B, S, h, dh, dtype=q.dtype, device=q.device)
     ops.bmm_strided(
         probs, v, o, layout=1, M=S, N=dh, K=S, nbatch=nb, heads=h, b_group=g,
@@ -826,21 +857,24 @@ class AttnPackedFn(torch.autograd.Function):
     """Attention over a PACKED qkv [B,S,3,h,dh] (BERT-style fused QKV):
     q/k/v are consumed as views, backward writes straight into one dqkv —
     zero permute/assembly copies on either pass. Fused flash kernels
-    (flash.hip) when eligible; materialized-scores path otherwise."""
+    (flash.hip) when eligible; materialized-scores path otherwise.
+    ``seq_lens`` (int32 [B] device tensor or None) is a non-differentiable
+    input handed to whichever path runs; it is never read on the host."""
 
     @staticmethod
-    def forward(ctx, qkv, causal):
+    def forward(ctx, qkv, causal, seq_lens=None):
         ops = require_hip()
         q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
         ctx.causal = causal
+        ctx.seq_lens = seq_lens
         if _flash_eligible(q, k, v):
             B, S, h, dh = q.shape
             o = torch.empty(B, S, h, dh, dtype=q.dtype, device=q.device)
-            _, lse = ops.flash_fwd(q, k, v, o, causal)
+            _, lse = ops.flash_fwd(q, k, v, o, causal, seq_lens)
             ctx.save_for_backward(qkv, o, lse)
             ctx.flash = True
             return o
-        o, probs = _attn_core_fwd(ops, q, k, v, causal)
+        o, probs = _attn_core_fwd(ops, q, k, v, causal, seq_lens)
         ctx.save_for_backward(qkv, probs)
         ctx.flash = False
         return o
@@ -855,27 +889,37 @@ class AttnPackedFn(torch.autograd.Function):
             dqkv = torch.empty_like(qkv)
             ops.flash_bwd(q, k, v, o, do, lse,
                           dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2],
-                          ctx.causal)
-            return dqkv, None
+                          ctx.causal, ctx.seq_lens)
+            return dqkv, None, None
         qkv, probs = ctx.saved_tensors
         dqkv = torch.empty_like(qkv)
         q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
         _attn_core_bwd(ops, q, k, v, probs, do,
                        dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2])
-        return dqkv, None
+        return dqkv, None, None
 
 
-def attention_qkv(qkv, causal: bool = False):
+def attention_qkv(qkv, causal: bool = False, seq_lens=None):
     """qkv: [B,S,3,h,dh] (one fused-projection tensor) -> o [B,S,h,dh].
     Packed layout implies equal q/k/v head counts (no GQA) — use
-    :func:`attention_bshd` with separate k/v views for grouped KV."""
+    :func:`attention_bshd` with separate k/v views for grouped KV.
+
+    ``seq_lens``: optional int32 [B] on qkv's device, 0 <= L_b <= S, for
+    right-padded batches. Key j is visible to query i iff j < L_b (and
+    j <= i if causal); the live rows equal the dense op on the [:L_b] slices
+    and rows >= L_b of o and of the qkv gradient are exactly 0. The lengths
+    stay on the device (a captured graph can carry them); validate them when
+    the data is prepared (``baton_amd.models.bert.lengths_from_mask``). The
+    flash path never reads the padded rows; the materialized-scores path
+    (fp32, dh outside {32,64,128}, BATON_NO_FLASH=1) multiplies them by
+    exact zeros and needs them finite."""
     assert qkv.dim() == 5 and qkv.shape[2] == 3, "qkv must be [B,S,3,h,dh]"
     if _on_gpu(qkv):
-        return AttnPackedFn.apply(qkv, causal)
+        return AttnPackedFn.apply(qkv, causal, seq_lens)
     B, S, _, h, dh = qkv.shape
     q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3).reshape(B * h, S, dh)
                for i in range(3))
-    o = attention(q, k, v, causal)
+    o = attention(q, k, v, causal, seq_lens, h)
     return o.reshape(B, h, S, dh).permute(0, 2, 1, 3)
 
 
@@ -884,17 +928,18 @@ class AttnBSHDFn(torch.autograd.Function):
     kv heads stay un-replicated AND un-permuted — strided views)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal):
+    def forward(ctx, q, k, v, causal, seq_lens=None):
         ops = require_hip()
         ctx.causal = causal
+        ctx.seq_lens = seq_lens
         if _flash_eligible(q, k, v):
             B, S, h, dh = q.shape
             o = torch.empty(B, S, h, dh, dtype=q.dtype, device=q.device)
-            _, lse = ops.flash_fwd(q, k, v, o, causal)
+            _, lse = ops.flash_fwd(q, k, v, o, causal, seq_lens)
             ctx.save_for_backward(q, k, v, o, lse)
             ctx.flash = True
             return o
-        o, probs = _attn_core_fwd(ops, q, k, v, causal)
+        o, probs = _attn_core_fwd(ops, q, k, v, causal, seq_lens)
         ctx.save_for_backward(q, k, v, probs)
         ctx.flash = False
         return o
@@ -909,7 +954,8 @@ class AttnBSHDFn(torch.autograd.Function):
         dv_qh = torch.empty_like(dq)
         if ctx.flash:
             q, k, v, o, lse = ctx.saved_tensors
-            ops.flash_bwd(q, k, v, o, do, lse, dq, dk_qh, dv_qh, ctx.causal)
+            ops.flash_bwd(q, k, v, o, do, lse, dq, dk_qh, dv_qh, ctx.causal,
+                          ctx.seq_lens)
         else:
             q, k, v, probs = ctx.saved_tensors
             _attn_core_bwd(ops, q, k, v, probs, do, dq, dk_qh, dv_qh)
@@ -920,19 +966,20 @@ class AttnBSHDFn(torch.autograd.Function):
             dv = dv_qh.view(B, S, kvh, g, dh).sum(3, dtype=torch.float32).to(do.dtype)
         else:
             dk, dv = dk_qh, dv_qh
-        return dq, dk, dv, None
+        return dq, dk, dv, None, None
 
 
-def attention_bshd(q, k, v, causal: bool = False):
-    """q: [B,S,h,dh]; k/v: [B,S,kvh,dh] (views allowed) -> o [B,S,h,dh]."""
+def attention_bshd(q, k, v, causal: bool = False, seq_lens=None):
+    """q: [B,S,h,dh]; k/v: [B,S,kvh,dh] (views allowed) -> o [B,S,h,dh].
+    ``seq_lens``: as in :func:`attention_qkv`."""
     if _on_gpu(q):
-        return AttnBSHDFn.apply(q, k, v, causal)
+        return AttnBSHDFn.apply(q, k, v, causal, seq_lens)
     B, S, h, dh = q.shape
     kvh = k.shape[2]
     qf = q.permute(0, 2, 1, 3).reshape(B * h, S, dh)
     kf = k.permute(0, 2, 1, 3).reshape(B * kvh, S, dh)
     vf = v.permute(0, 2, 1, 3).reshape(B * kvh, S, dh)
-    o = attention(qf, kf, vf, causal)
+    o = attention(qf, kf, vf, causal, seq_lens, h)
     return o.reshape(B, h, S, dh).permute(0, 2, 1, 3)
 
 

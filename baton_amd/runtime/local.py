@@ -32,6 +32,11 @@ class LocalTrainer:
     ``data`` is the tuple from ``ExperimentWorker.get_data()`` — positional
     tensors whose first dim is the sample dim; the last tensor is the target.
     ``loss_fn`` maps (model_output, target) -> scalar loss.
+
+    Every tensor before the target is a model input and is minibatched with
+    it: ``data = (ids, seq_lens, labels)`` calls ``model(ids, seq_lens)``
+    (right-padded batches, models/bert.py). The captured per-minibatch graph
+    step takes a single input, so data with more than one input runs eagerly.
     """
 
     def __init__(

@@ -259,65 +259,98 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
   return dx;
 }
 
-// ---- layernorm -------------------------------------------------------------
+// ---- layernorm / rmsnorm -----------------------------------------------------
+// One forward and one backward for both families and their fused forms:
+// center = LayerNorm (b, mean, db exist), res / plus = the fused residual add
+// (z = x + res is returned after y) / residual-stream gradient (dx += plus).
+
+static std::vector<at::Tensor> norm_rows_fwd(const char* op, bool center,
+                                             const at::Tensor& x,
+                                             const at::Tensor* res,
+                                             const at::Tensor& w,
+                                             const at::Tensor* b, double eps) {
+  const NormShape sh = norm_shape(x, op, center);
+  const int C = sh.C;
+  const long long R = sh.R;
+  if (res) norm_check_like_x(*res, "res", x, op);
+  norm_check_vec(w, "w", x, x.scalar_type(), C, op);
+  if (center) norm_check_vec(*b, "b", x, x.scalar_type(), C, op);
+  auto y = at::empty_like(x);
+  at::Tensor z = res ? at::empty_like(x) : at::Tensor();
+  auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
+  at::Tensor mean = center ? at::empty_like(rstd) : at::Tensor();
+  launch_norm_fwd(norm_row_route(R, C, is_bf16(x)), is_bf16(x), center,
+                  x.data_ptr(), res ? res->data_ptr() : nullptr, w.data_ptr(),
+                  center ? b->data_ptr() : nullptr, y.data_ptr(),
+                  res ? z.data_ptr() : nullptr,
+                  center ? mean.data_ptr<float>() : nullptr,
+                  rstd.data_ptr<float>(), R, C, (float)eps, stream());
+  std::vector<at::Tensor> out{y};
+  if (res) out.push_back(z);
+  if (center) out.push_back(mean);
+  out.push_back(rstd);
+  return out;
+}
+
+static std::vector<at::Tensor> norm_rows_bwd(const char* op, bool center,
+                                             const at::Tensor& x,
+                                             const at::Tensor& dy,
+                                             const at::Tensor& w,
+                                             const at::Tensor* mean,
+                                             const at::Tensor& rstd,
+                                             const at::Tensor* plus) {
+  const NormShape sh = norm_shape(x, op, center);
+  const int C = sh.C;
+  const long long R = sh.R;
+  norm_check_like_x(dy, "dy", x, op);
+  if (plus) norm_check_like_x(*plus, "plus", x, op);
+  norm_check_vec(w, "w", x, x.scalar_type(), C, op);
+  if (center) norm_check_vec(*mean, "mean", x, at::kFloat, R, op);
+  norm_check_vec(rstd, "rstd", x, at::kFloat, R, op);
+  auto dx = at::empty_like(x);
+  auto dw = at::zeros({C}, x.options().dtype(at::kFloat));
+  at::Tensor db = center ? at::zeros_like(dw) : at::Tensor();
+  launch_norm_bwd(norm_row_route(R, C, is_bf16(x)), is_bf16(x), center,
+                  x.data_ptr(), dy.data_ptr(), w.data_ptr(),
+                  center ? mean->data_ptr<float>() : nullptr,
+                  rstd.data_ptr<float>(), plus ? plus->data_ptr() : nullptr,
+                  dx.data_ptr(), dw.data_ptr<float>(),
+                  center ? db.data_ptr<float>() : nullptr, R, C, stream());
+  if (center) return {dx, dw, db};
+  return {dx, dw};
+}
 
 std::vector<at::Tensor> ln_fwd(at::Tensor x, at::Tensor w, at::Tensor b,
                                double eps) {
-  const NormShape sh = norm_shape(x, "ln_fwd", true);
-  const int C = sh.C;
-  const long long R = sh.R;
-  norm_check_vec(w, "w", x, x.scalar_type(), C, "ln_fwd");
-  norm_check_vec(b, "b", x, x.scalar_type(), C, "ln_fwd");
-  auto y = at::empty_like(x);
-  auto mean = at::empty({R}, x.options().dtype(at::kFloat));
-  auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
-  launch_ln_fwd(is_bf16(x), x.data_ptr(), nullptr, w.data_ptr(), b.data_ptr(),
-                y.data_ptr(), nullptr, mean.data_ptr<float>(),
-                rstd.data_ptr<float>(), (int)R, C, (float)eps, stream());
-  return {y, mean, rstd};
+  return norm_rows_fwd("ln_fwd", true, x, nullptr, w, &b, eps);
 }
-
-// fused residual-add + LayerNorm: y = LN(x + res); also returns z = x + res
-// (saved for backward / reused as the residual stream)
 std::vector<at::Tensor> ln_add_fwd(at::Tensor x, at::Tensor res, at::Tensor w,
                                    at::Tensor b, double eps) {
-  const NormShape sh = norm_shape(x, "ln_add_fwd", true);
-  const int C = sh.C;
-  const long long R = sh.R;
-  norm_check_like_x(res, "res", x, "ln_add_fwd");
-  norm_check_vec(w, "w", x, x.scalar_type(), C, "ln_add_fwd");
-  norm_check_vec(b, "b", x, x.scalar_type(), C, "ln_add_fwd");
-  auto y = at::empty_like(x);
-  auto z = at::empty_like(x);
-  auto mean = at::empty({R}, x.options().dtype(at::kFloat));
-  auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
-  launch_ln_fwd(is_bf16(x), x.data_ptr(), res.data_ptr(), w.data_ptr(),
-                b.data_ptr(), y.data_ptr(), z.data_ptr(),
-                mean.data_ptr<float>(), rstd.data_ptr<float>(), (int)R, C,
-                (float)eps, stream());
-  return {y, z, mean, rstd};
+  return norm_rows_fwd("ln_add_fwd", true, x, &res, w, &b, eps);
 }
-
 std::vector<at::Tensor> ln_bwd(at::Tensor x, at::Tensor dy, at::Tensor w,
                                at::Tensor mean, at::Tensor rstd) {
-  const NormShape sh = norm_shape(x, "ln_bwd", true);
-  const int C = sh.C;
-  const long long R = sh.R;
-  norm_check_like_x(dy, "dy", x, "ln_bwd");
-  norm_check_vec(w, "w", x, x.scalar_type(), C, "ln_bwd");
-  norm_check_vec(mean, "mean", x, at::kFloat, R, "ln_bwd");
-  norm_check_vec(rstd, "rstd", x, at::kFloat, R, "ln_bwd");
-  auto dx = at::empty_like(x);
-  auto dw = at::zeros({C}, x.options().dtype(at::kFloat));
-  auto db = at::zeros({C}, x.options().dtype(at::kFloat));
-  launch_ln_bwd_dx(is_bf16(x), x.data_ptr(), dy.data_ptr(), w.data_ptr(),
-                   mean.data_ptr<float>(), rstd.data_ptr<float>(), nullptr,
-                   dx.data_ptr(), (int)R, C, stream());
-  launch_ln_bwd_dwdb(is_bf16(x), x.data_ptr(), dy.data_ptr(),
-                     mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                     dw.data_ptr<float>(), db.data_ptr<float>(), (int)R, C,
-                     stream());
-  return {dx, dw, db};
+  return norm_rows_bwd("ln_bwd", true, x, dy, w, &mean, rstd, nullptr);
+}
+std::vector<at::Tensor> ln_bwd_plus(at::Tensor x, at::Tensor dy, at::Tensor w,
+                                    at::Tensor mean, at::Tensor rstd,
+                                    at::Tensor plus) {
+  return norm_rows_bwd("ln_bwd_plus", true, x, dy, w, &mean, rstd, &plus);
+}
+std::vector<at::Tensor> rms_fwd(at::Tensor x, at::Tensor w, double eps) {
+  return norm_rows_fwd("rms_fwd", false, x, nullptr, w, nullptr, eps);
+}
+std::vector<at::Tensor> rms_add_fwd(at::Tensor x, at::Tensor res, at::Tensor w,
+                                    double eps) {
+  return norm_rows_fwd("rms_add_fwd", false, x, &res, w, nullptr, eps);
+}
+std::vector<at::Tensor> rms_bwd(at::Tensor x, at::Tensor dy, at::Tensor w,
+                                at::Tensor rstd) {
+  return norm_rows_bwd("rms_bwd", false, x, dy, w, nullptr, rstd, nullptr);
+}
+std::vector<at::Tensor> rms_bwd_plus(at::Tensor x, at::Tensor dy, at::Tensor w,
+                                     at::Tensor rstd, at::Tensor plus) {
+  return norm_rows_bwd("rms_bwd_plus", false, x, dy, w, nullptr, rstd, &plus);
 }
 
 // ---- batchnorm (x viewed as [M, C], i.e. NHWC flattened) -------------------
@@ -354,14 +387,15 @@ std::vector<at::Tensor> bn_fwd_train(at::Tensor x, at::Tensor gamma,
   auto mean = at::empty({C}, x.options().dtype(at::kFloat));
   auto rstd = at::empty({C}, x.options().dtype(at::kFloat));
   auto y = at::empty_like(x);
-  launch_bn_stats(is_bf16(x), x.data_ptr(), sum.data_ptr<float>(),
+  const BnRoute rt = bn_route(M, C, is_bf16(x));
+  launch_bn_stats(rt, is_bf16(x), x.data_ptr(), sum.data_ptr<float>(),
                   sumsq.data_ptr<float>(), M, C, stream());
   float* rm = has_running ? running_mean.data_ptr<float>() : nullptr;
   float* rv = has_running ? running_var.data_ptr<float>() : nullptr;
   launch_bn_finalize(sum.data_ptr<float>(), sumsq.data_ptr<float>(),
                      mean.data_ptr<float>(), rstd.data_ptr<float>(), rm, rv, M,
                      C, (float)eps, (float)momentum, stream());
-  launch_bn_norm(is_bf16(x), relu, x.data_ptr(),
+  launch_bn_norm(rt, is_bf16(x), relu, x.data_ptr(),
                  has_res ? res.data_ptr() : nullptr, mean.data_ptr<float>(),
                  rstd.data_ptr<float>(), gamma.data_ptr<float>(),
                  beta.data_ptr<float>(), y.data_ptr(), M, C, stream());
@@ -378,7 +412,8 @@ at::Tensor bn_fwd_eval(at::Tensor x, at::Tensor gamma, at::Tensor beta,
   norm_check_vec(mean, "mean", x, at::kFloat, C, "bn_fwd_eval");
   norm_check_vec(rstd, "rstd", x, at::kFloat, C, "bn_fwd_eval");
   auto y = at::empty_like(x);
-  launch_bn_norm(is_bf16(x), relu, x.data_ptr(), nullptr,
+  launch_bn_norm(bn_route(M, C, is_bf16(x)), is_bf16(x), relu, x.data_ptr(),
+                 nullptr,
                  mean.data_ptr<float>(), rstd.data_ptr<float>(), gamma.data_ptr<float>(),
                  beta.data_ptr<float>(), y.data_ptr(), M, C, stream());
   return y;
@@ -395,11 +430,9 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor y_post,
   norm_check_vec(mean, "mean", x, at::kFloat, C, "bn_bwd");
   norm_check_vec(rstd, "rstd", x, at::kFloat, C, "bn_bwd");
   norm_check_vec(gamma, "gamma", x, at::kFloat, C, "bn_bwd");
-  if (want_dres) {
-    const int velems = is_bf16(x) ? 8 : 4;
-    TORCH_CHECK(relu && (C % velems) == 0 && C <= 4096,
-                "bn dres needs the fused-relu vectorized path");
-  }
+  const BnRoute rt = bn_route(M, C, is_bf16(x));
+  TORCH_CHECK(!want_dres || (relu && rt.dres_ok),
+              "bn dres needs the fused-relu vectorized path");
   auto sum_dy = at::zeros({C}, x.options().dtype(at::kFloat));
   auto sum_dyx = at::zeros({C}, x.options().dtype(at::kFloat));
   auto dx = at::empty_like(x);
@@ -412,12 +445,12 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor y_post,
     dres_ptr = dres.data_ptr();
   }
   const void* ypost_ptr = relu ? y_post.data_ptr() : x.data_ptr();
-  launch_bn_bwd_stats(is_bf16(x), relu, x.data_ptr(), dy.data_ptr(), ypost_ptr,
-                      mean.data_ptr<float>(), rstd.data_ptr<float>(),
+  launch_bn_bwd_stats(rt, is_bf16(x), relu, x.data_ptr(), dy.data_ptr(),
+                      ypost_ptr, mean.data_ptr<float>(), rstd.data_ptr<float>(),
                       sum_dy.data_ptr<float>(), sum_dyx.data_ptr<float>(), M, C,
                       stream());
-  launch_bn_bwd_dx(is_bf16(x), relu, x.data_ptr(), dy.data_ptr(), ypost_ptr,
-                   mean.data_ptr<float>(), rstd.data_ptr<float>(),
+  launch_bn_bwd_dx(rt, is_bf16(x), relu, x.data_ptr(), dy.data_ptr(),
+                   ypost_ptr, mean.data_ptr<float>(), rstd.data_ptr<float>(),
                    gamma.data_ptr<float>(), sum_dy.data_ptr<float>(),
                    sum_dyx.data_ptr<float>(), dx.data_ptr(), dres_ptr, M, C,
                    stream());
@@ -753,6 +786,32 @@ py::dict conv_route_py(const std::string& op, int64_t N, int64_t H, int64_t W,
 }
 
 
+// What norm_route.h decides for [rows, C]: family "ln" / "rms" (rows = R) or
+// "bn" (rows = M). The norm ops above launch exactly this.
+py::dict norm_route_py(const std::string& family, int64_t rows, int64_t C,
+                       bool bf16) {
+  using namespace py::literals;
+  TORCH_CHECK(family == "ln" || family == "rms" || family == "bn",
+              "norm_route: family must be ln, rms or bn");
+  TORCH_CHECK(rows > 0 && C > 0 && C <= INT_MAX, "norm_route: bad shape");
+  if (family != "bn") {
+    const NormRowRoute rt = norm_row_route(rows, (int)C, bf16);
+    return py::dict("vec"_a = rt.vec, "trips"_a = rt.trips, "grid"_a = rt.grid,
+                    "capped"_a = rt.capped, "chunks"_a = rt.chunks,
+                    "rows_per_block"_a = rt.rows_per_block,
+                    "grid_y"_a = rt.grid_y,
+                    "direct_store"_a = rt.direct_store);
+  }
+  const BnRoute rt = bn_route(rows, (int)C, bf16);
+  return py::dict(
+      "stats"_a = rt.stats_vec ? "vec" : "scalar", "chunks"_a = rt.chunks,
+      "rows_per_block"_a = rt.rows_per_block, "grid_y"_a = rt.grid_y,
+      "norm"_a = rt.norm_vec ? "vec" : "scalar", "norm_trips"_a = rt.norm_trips,
+      "dx"_a = rt.dx_vec ? "vec" : "scalar", "dx_trips"_a = rt.dx_trips,
+      "dres_ok"_a = rt.dres_ok, "elem_grid"_a = rt.elem_grid,
+      "norm_lds"_a = rt.norm_lds, "dx_lds"_a = rt.dx_lds);
+}
+
 // The index maps of the pixel-major 3x3 wgrad (wgrad_px_map.h) for one
 // k-step, as plain lists: checkable on a machine with no GPU. The kernel
 // calls the same functions.
@@ -1004,94 +1063,6 @@ at::Tensor softmax_bwd(at::Tensor y, at::Tensor dy, double scale) {
 
 // ---- llama ops -------------------------------------------------------------
 
-std::vector<at::Tensor> rms_fwd(at::Tensor x, at::Tensor w, double eps) {
-  const NormShape sh = norm_shape(x, "rms_fwd", false);
-  const int C = sh.C;
-  const long long R = sh.R;
-  norm_check_vec(w, "w", x, x.scalar_type(), C, "rms_fwd");
-  auto y = at::empty_like(x);
-  auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
-  launch_rms_fwd(is_bf16(x), x.data_ptr(), nullptr, w.data_ptr(), y.data_ptr(),
-                 nullptr, rstd.data_ptr<float>(), R, C, (float)eps, stream());
-  return {y, rstd};
-}
-
-// fused residual-add + RMSNorm: y = RMS(x + res), z = x + res returned for
-// the residual stream and backward
-std::vector<at::Tensor> rms_add_fwd(at::Tensor x, at::Tensor res, at::Tensor w,
-                                    double eps) {
-  const NormShape sh = norm_shape(x, "rms_add_fwd", false);
-  const int C = sh.C;
-  const long long R = sh.R;
-  norm_check_like_x(res, "res", x, "rms_add_fwd");
-  norm_check_vec(w, "w", x, x.scalar_type(), C, "rms_add_fwd");
-  auto y = at::empty_like(x);
-  auto z = at::empty_like(x);
-  auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
-  launch_rms_fwd(is_bf16(x), x.data_ptr(), res.data_ptr(), w.data_ptr(),
-                 y.data_ptr(), z.data_ptr(), rstd.data_ptr<float>(), R, C,
-                 (float)eps, stream());
-  return {y, z, rstd};
-}
-
-std::vector<at::Tensor> rms_bwd(at::Tensor x, at::Tensor dy, at::Tensor w,
-                                at::Tensor rstd) {
-  const NormShape sh = norm_shape(x, "rms_bwd", false);
-  const int C = sh.C;
-  const long long R = sh.R;
-  norm_check_like_x(dy, "dy", x, "rms_bwd");
-  norm_check_vec(w, "w", x, x.scalar_type(), C, "rms_bwd");
-  norm_check_vec(rstd, "rstd", x, at::kFloat, R, "rms_bwd");
-  auto dx = at::empty_like(x);
-  auto dw = at::zeros({C}, x.options().dtype(at::kFloat));
-  launch_rms_bwd(is_bf16(x), x.data_ptr(), dy.data_ptr(), w.data_ptr(),
-                 rstd.data_ptr<float>(), nullptr, dx.data_ptr(),
-                 dw.data_ptr<float>(), R, C, stream());
-  return {dx, dw};
-}
-
-std::vector<at::Tensor> rms_bwd_plus(at::Tensor x, at::Tensor dy, at::Tensor w,
-                                     at::Tensor rstd, at::Tensor plus) {
-  const NormShape sh = norm_shape(x, "rms_bwd_plus", false);
-  const int C = sh.C;
-  const long long R = sh.R;
-  norm_check_like_x(dy, "dy", x, "rms_bwd_plus");
-  norm_check_like_x(plus, "plus", x, "rms_bwd_plus");
-  norm_check_vec(w, "w", x, x.scalar_type(), C, "rms_bwd_plus");
-  norm_check_vec(rstd, "rstd", x, at::kFloat, R, "rms_bwd_plus");
-  auto dx = at::empty_like(x);
-  auto dw = at::zeros({C}, x.options().dtype(at::kFloat));
-  launch_rms_bwd(is_bf16(x), x.data_ptr(), dy.data_ptr(), w.data_ptr(),
-                 rstd.data_ptr<float>(), plus.data_ptr(), dx.data_ptr(),
-                 dw.data_ptr<float>(), R, C, stream());
-  return {dx, dw};
-}
-
-// ln_bwd with the residual-stream gradient fused into dx (dx += plus)
-std::vector<at::Tensor> ln_bwd_plus(at::Tensor x, at::Tensor dy, at::Tensor w,
-                                    at::Tensor mean, at::Tensor rstd,
-                                    at::Tensor plus) {
-  const NormShape sh = norm_shape(x, "ln_bwd_plus", true);
-  const int C = sh.C;
-  const long long R = sh.R;
-  norm_check_like_x(dy, "dy", x, "ln_bwd_plus");
-  norm_check_like_x(plus, "plus", x, "ln_bwd_plus");
-  norm_check_vec(w, "w", x, x.scalar_type(), C, "ln_bwd_plus");
-  norm_check_vec(mean, "mean", x, at::kFloat, R, "ln_bwd_plus");
-  norm_check_vec(rstd, "rstd", x, at::kFloat, R, "ln_bwd_plus");
-  auto dx = at::empty_like(x);
-  auto dw = at::zeros({C}, x.options().dtype(at::kFloat));
-  auto db = at::zeros({C}, x.options().dtype(at::kFloat));
-  launch_ln_bwd_dx(is_bf16(x), x.data_ptr(), dy.data_ptr(), w.data_ptr(),
-                   mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                   plus.data_ptr(), dx.data_ptr(), (int)R, C, stream());
-  launch_ln_bwd_dwdb(is_bf16(x), x.data_ptr(), dy.data_ptr(),
-                     mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                     dw.data_ptr<float>(), db.data_ptr<float>(), (int)R, C,
-                     stream());
-  return {dx, dw, db};
-}
-
 at::Tensor rope(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t,
                 bool inverse) {
   check_compute(x, "x");
@@ -1334,6 +1305,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"),
         py::arg("KH"), py::arg("KW"), py::arg("stride"), py::arg("pad"),
         py::arg("bf16") = true);
+  m.def("norm_route", &norm_route_py, py::arg("family"), py::arg("rows"),
+        py::arg("C"), py::arg("bf16"));
   m.def("conv_fwd", &conv_fwd);
   m.def("conv_dgrad", &conv_dgrad);
   m.def("conv_wgrad", &conv_wgrad);

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <type_traits>
+
 #define DEVINL __device__ __forceinline__
 
 constexpr int kWave = 64;           // CDNA wavefront width (not 32)
@@ -92,6 +94,34 @@ DEVINL void vstore16(T* p, const float* f) {
   typename VT::VecT v;
   VT::from_float(f, v);
   *reinterpret_cast<typename VT::VecT*>(p) = v;
+}
+
+// Width-generic forms: W == VecTraits<T>::kElems is the 16-B vector, W == 1
+// one element.
+template <int W, typename T>
+DEVINL void vload(const T* p, float* f) {
+  if constexpr (W == 1) f[0] = (float)p[0];
+  else vload16(p, f);
+}
+template <int W, typename T>
+DEVINL void vstore(T* p, const float* f) {
+  if constexpr (W == 1) p[0] = (T)f[0];
+  else vstore16(p, f);
+}
+
+// Row walker: the block's threads stride a row of C elements, as 16-B vectors
+// when C % V == 0 (wave-uniform) and element by element otherwise. Calls
+// body(element offset, integral_constant<int, W>) with W = V or 1.
+template <typename T, typename F>
+DEVINL void row_walk(int C, F&& body) {
+  constexpr int V = VecTraits<T>::kElems;
+  if ((C % V) == 0) {
+    for (int cv = threadIdx.x; cv < C / V; cv += blockDim.x)
+      body(cv * V, std::integral_constant<int, V>{});
+  } else {
+    for (int c = threadIdx.x; c < C; c += blockDim.x)
+      body(c, std::integral_constant<int, 1>{});
+  }
 }
 
 // ---- reductions ----------------------------------------------------------

@@ -7,6 +7,7 @@
 #include "conv_route.h"
 #include "gemm_plan.h"
 #include "gemm_strides.h"
+#include "norm_route.h"
 
 // optim.hip
 void launch_sgd(bool is_bf16, void* p, void* g, float* m, long long n,
@@ -37,35 +38,38 @@ void launch_ce_bwd(bool is_bf16, const void* logits, const long long* target,
                    const float* lse, const float* dout, void* dx, int B, int C,
                    hipStream_t s);
 
-// norm.hip
-void launch_ln_fwd(bool is_bf16, const void* x, const void* res, const void* w,
-                   const void* b, void* y, void* zout, float* mean,
-                   float* rstd, int R, int C, float eps, hipStream_t s);
-void launch_ln_bwd_dx(bool is_bf16, const void* x, const void* dy, const void* w,
-                      const float* mean, const float* rstd, const void* plus,
-                      void* dx, int R, int C, hipStream_t s);
-void launch_ln_bwd_dwdb(bool is_bf16, const void* x, const void* dy,
-                        const float* mean, const float* rstd, float* dw,
-                        float* db, int R, int C, hipStream_t s);
-void launch_bn_stats(bool is_bf16, const void* x, float* sum, float* sumsq,
-                     long long M, int C, hipStream_t s);
+// norm.hip — LayerNorm (center) / RMSNorm rows and BatchNorm: each launches
+// exactly the grid, kernel form and LDS size the route names (norm_route.h
+// decides). res / plus / dres select the fused forms when not nullptr; b,
+// mean and db are LayerNorm's alone.
+void launch_norm_fwd(const NormRowRoute& rt, bool is_bf16, bool center,
+                     const void* x, const void* res, const void* w,
+                     const void* b, void* y, void* zout, float* mean,
+                     float* rstd, long long R, int C, float eps, hipStream_t s);
+void launch_norm_bwd(const NormRowRoute& rt, bool is_bf16, bool center,
+                     const void* x, const void* dy, const void* w,
+                     const float* mean, const float* rstd, const void* plus,
+                     void* dx, float* dw, float* db, long long R, int C,
+                     hipStream_t s);
+void launch_bn_stats(const BnRoute& rt, bool is_bf16, const void* x, float* sum,
+                     float* sumsq, long long M, int C, hipStream_t s);
 void launch_bn_finalize(const float* sum, const float* sumsq, float* mean,
                         float* rstd, float* running_mean, float* running_var,
                         long long M, int C, float eps, float momentum,
                         hipStream_t s);
-void launch_bn_norm(bool is_bf16, bool relu, const void* x, const void* res,
-                    const float* mean,
-                    const float* rstd, const float* gamma, const float* beta,
-                    void* y, long long M, int C, hipStream_t s);
-void launch_bn_bwd_stats(bool is_bf16, bool relu, const void* x, const void* dy,
-                         const void* y_post, const float* mean,
-                         const float* rstd, float* sum_dy, float* sum_dyx,
-                         long long M, int C, hipStream_t s);
-void launch_bn_bwd_dx(bool is_bf16, bool relu, const void* x, const void* dy,
-                      const void* y_post, const float* mean, const float* rstd,
-                      const float* gamma, const float* sum_dy,
-                      const float* sum_dyx, void* dx, void* dres, long long M,
-                      int C, hipStream_t s);
+void launch_bn_norm(const BnRoute& rt, bool is_bf16, bool relu, const void* x,
+                    const void* res, const float* mean, const float* rstd,
+                    const float* gamma, const float* beta, void* y, long long M,
+                    int C, hipStream_t s);
+void launch_bn_bwd_stats(const BnRoute& rt, bool is_bf16, bool relu,
+                         const void* x, const void* dy, const void* y_post,
+                         const float* mean, const float* rstd, float* sum_dy,
+                         float* sum_dyx, long long M, int C, hipStream_t s);
+void launch_bn_bwd_dx(const BnRoute& rt, bool is_bf16, bool relu, const void* x,
+                      const void* dy, const void* y_post, const float* mean,
+                      const float* rstd, const float* gamma,
+                      const float* sum_dy, const float* sum_dyx, void* dx,
+                      void* dres, long long M, int C, hipStream_t s);
 
 // elementwise.hip
 void launch_relu_fwd(bool is_bf16, const void* x, void* y, long long n,
@@ -140,13 +144,7 @@ void launch_softmax_fwd(bool is_bf16, const void* x, void* y, long long R,
 void launch_softmax_bwd(bool is_bf16, const void* y, const void* dy, void* dx,
                         long long R, int C, float scale, hipStream_t s);
 
-// llama_ops.hip — RMSNorm / RoPE / SwiGLU
-void launch_rms_fwd(bool is_bf16, const void* x, const void* res,
-                    const void* w, void* y, void* zout, float* rstd,
-                    long long R, int C, float eps, hipStream_t s);
-void launch_rms_bwd(bool is_bf16, const void* x, const void* dy, const void* w,
-                    const float* rstd, const void* plus, void* dx, float* dw,
-                    long long R, int C, hipStream_t s);
+// llama_ops.hip — RoPE / SwiGLU
 void launch_rope(bool is_bf16, bool inverse, const void* x, void* y,
                  const float* cos_t, const float* sin_t, long long total_pairs,
                  int S, int H, int D, hipStream_t s);

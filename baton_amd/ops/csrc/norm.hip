@@ -1,212 +1,275 @@
-// Normalization kernels (gfx950): LayerNorm + BatchNorm (NHWC), fwd + bwd.
+// Normalization kernels (gfx950): LayerNorm, RMSNorm and BatchNorm (NHWC),
+// fwd + bwd. norm_route.h decides every grid and kernel form; the launchers
+// at the end launch exactly what a route names.
 //
 // Not present in the reference (SURVEY.md §2.2 — its only model is
-// Linear(10,1)) but required by the ResNet/BERT federated configs.
+// Linear(10,1)) but required by the ResNet / BERT / Llama federated configs.
 //
-// LayerNorm: one block per row, block-reduced mean/var, saved (mean, rstd)
-// for backward; dgamma/dbeta by a column-chunk reduction kernel (no
-// atomics — each block owns a channel chunk and walks rows, coalesced in
-// NHWC/row-major since consecutive lanes read consecutive channels).
-// BatchNorm (training): per-channel stats by column-chunk reduction with a
-// rows-split atomicAdd pass, then a vectorized normalize pass; eval mode
-// normalizes with running stats.
+// LayerNorm / RMSNorm: one block per row, block-reduced statistics, saved
+// (mean, rstd) for backward; dgamma / dbeta by a column-chunk reduction
+// (coalesced in NHWC / row-major since consecutive lanes read consecutive
+// channels). BatchNorm (training): per-channel stats by column-chunk
+// reduction with a rows-split atomicAdd pass, then a vectorized normalize
+// pass; eval mode normalizes with running stats.
 #include "common.h"
+#include "norm_route.h"
 
-// ---- LayerNorm forward -----------------------------------------------------
+static_assert(kNormBlock == kBlock && kNormMaxGrid == kMaxGrid,
+              "norm_route.h sizes its grids for common.h's block and cap");
 
-// ADD fuses the transformer residual add: z = x + res is written once and
-// normalized in place (the at::add glue kernels).
-template <typename T, bool ADD>
-__global__ void ln_fwd_kernel(const T* __restrict__ x,
-                              const T* __restrict__ res, const T* __restrict__ w,
-                              const T* __restrict__ b, T* __restrict__ y,
-                              T* __restrict__ zout,
-                              float* __restrict__ mean_out,
-                              float* __restrict__ rstd_out, int R, int C,
-                              float eps) {
+// Row index of the row kernels: LayerNorm's rows fit int (bindings.cpp
+// refuses more) and its kernels keep the int loop. Under the 64-bit loop that
+// RMSNorm needs, LayerNorm's forward took up to 8 more VGPRs and the dx pass
+// of ln_bwd_plus ran 1.5x as long (profiles/r06_norm_refactor.md).
+template <bool MEAN>
+using NormRow = std::conditional_t<MEAN, int, long long>;
+
+// ---- LayerNorm / RMSNorm forward ---------------------------------------------
+// MEAN (LayerNorm): y = (x - mu) rstd w + b, rstd = (var + eps)^-1/2 from the
+// one-pass variance; saves (mean, rstd). Without MEAN (RMSNorm): y = x rstd w,
+// rstd = (mean(x^2) + eps)^-1/2; saves rstd, b and mean_out are not touched.
+// ADD fuses the transformer residual add (guide: fuse elementwise work into
+// the producing pass): z = x + res is written ONCE here and the norm consumes
+// it — the separate add kernel and one full tensor read disappear (the
+// at::add glue in the r1 profiles, VERDICT weak #4).
+template <typename T, bool MEAN, bool ADD>
+__global__ void norm_fwd_kernel(const T* __restrict__ x,
+                                const T* __restrict__ res,
+                                const T* __restrict__ w, const T* __restrict__ b,
+                                T* __restrict__ y, T* __restrict__ zout,
+                                float* __restrict__ mean_out,
+                                float* __restrict__ rstd_out, long long R, int C,
+                                float eps) {
   __shared__ float scratch[kBlock / kWave];
-  for (int r = blockIdx.x; r < R; r += gridDim.x) {
-    const T* row = x + (long long)r * C;
-    T* yrow = y + (long long)r * C;
-    constexpr int V = VecTraits<T>::kElems;
-    const bool vec = (C % V) == 0;      // wave-uniform
+  using Row = NormRow<MEAN>;
+  for (Row r = blockIdx.x; r < (Row)R; r += gridDim.x) {
+    const long long base = (long long)r * C;
+    const T* row = x + base;
+    T* yrow = y + base;
     float s = 0.f, ss = 0.f;
-    if (vec) {
-      for (int cv = threadIdx.x; cv < C / V; cv += blockDim.x) {
-        float f[V];
-        vload16(row + cv * V, f);
-        if (ADD) {
-          float fr[V];
-          vload16(res + (long long)r * C + cv * V, fr);
+    row_walk<T>(C, [&](int c, auto width) {
+      constexpr int W = decltype(width)::value;
+      float f[W];
+      vload<W>(row + c, f);
+      if constexpr (ADD) {
+        float fr[W];
+        vload<W>(res + base + c, fr);
 #pragma unroll
-          for (int q = 0; q < V; ++q) f[q] += fr[q];
-          vstore16(zout + (long long)r * C + cv * V, f);
-        }
-#pragma unroll
-        for (int q = 0; q < V; ++q) {
-          s += f[q];
-          ss = fmaf(f[q], f[q], ss);
-        }
+        for (int q = 0; q < W; ++q) f[q] += fr[q];
+        vstore<W>(zout + base + c, f);
       }
+#pragma unroll
+      for (int q = 0; q < W; ++q) {
+        if constexpr (MEAN) s += f[q];
+        ss = fmaf(f[q], f[q], ss);
+      }
+    });
+    float mu = 0.f, rstd;
+    if constexpr (MEAN) {
+      float sum = block_reduce_sum(s, scratch);
+      float sumsq = block_reduce_sum(ss, scratch);
+      mu = sum / C;
+      float var = sumsq / C - mu * mu;
+      rstd = rsqrtf(fmaxf(var, 0.f) + eps);
     } else {
-      for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float v = (float)row[c];
-        if (ADD) {
-          v += (float)res[(long long)r * C + c];
-          zout[(long long)r * C + c] = (T)v;
-        }
-        s += v;
-        ss = fmaf(v, v, ss);
-      }
+      float sumsq = block_reduce_sum(ss, scratch);
+      rstd = rsqrtf(sumsq / C + eps);
     }
-    float sum = block_reduce_sum(s, scratch);
-    float sumsq = block_reduce_sum(ss, scratch);
-    float mu = sum / C;
-    float var = sumsq / C - mu * mu;
-    float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
     if (threadIdx.x == 0) {
-      mean_out[r] = mu;
+      if constexpr (MEAN) mean_out[r] = mu;
       rstd_out[r] = rstd;
     }
-    const T* zrow = ADD ? zout + (long long)r * C : row;
-    if (vec) {
-      for (int cv = threadIdx.x; cv < C / V; cv += blockDim.x) {
-        float f[V], fw[V], fb[V];
-        vload16(zrow + cv * V, f);
-        vload16(w + cv * V, fw);
-        vload16(b + cv * V, fb);
+    // normalize pass re-reads the summed row (same CU wrote it; the
+    // inter-CU L1 staleness hazard does not apply to a block's own lines)
+    const T* zrow = ADD ? zout + base : row;
+    row_walk<T>(C, [&](int c, auto width) {
+      constexpr int W = decltype(width)::value;
+      float f[W], fw[W];
+      vload<W>(zrow + c, f);
+      vload<W>(w + c, fw);
+      if constexpr (MEAN) {
+        float fb[W];
+        vload<W>(b + c, fb);
 #pragma unroll
-        for (int q = 0; q < V; ++q)
+        for (int q = 0; q < W; ++q)
           f[q] = fmaf((f[q] - mu) * rstd, fw[q], fb[q]);
-        vstore16(yrow + cv * V, f);
+      } else {
+#pragma unroll
+        for (int q = 0; q < W; ++q) f[q] = f[q] * rstd * fw[q];
       }
-    } else {
-      for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float xhat = ((float)zrow[c] - mu) * rstd;
-        yrow[c] = (T)fmaf(xhat, (float)w[c], (float)b[c]);
-      }
-    }
+      vstore<W>(yrow + c, f);
+    });
   }
 }
 
-// ---- LayerNorm backward (dx) ----------------------------------------------
-// dx = rstd * (dyg - mean(dyg) - xhat * mean(dyg*xhat)), dyg = dy*gamma
-
-// PLUS fuses the residual-stream gradient add (backward of z = x + res).
-template <typename T, bool PLUS>
-__global__ void ln_bwd_dx_kernel(const T* __restrict__ x, const T* __restrict__ dy,
-                                 const T* __restrict__ w,
-                                 const float* __restrict__ mean,
-                                 const float* __restrict__ rstd,
-                                 const T* __restrict__ plus,
-                                 T* __restrict__ dx, int R, int C) {
-  __shared__ float scratch[kBlock / kWave];
-  for (int r = blockIdx.x; r < R; r += gridDim.x) {
-    const T* xrow = x + (long long)r * C;
-    const T* dyrow = dy + (long long)r * C;
-    T* dxrow = dx + (long long)r * C;
-    const float mu = mean[r], rs = rstd[r];
-    constexpr int V = VecTraits<T>::kElems;
-    const bool vec = (C % V) == 0;      // wave-uniform
-    float s1 = 0.f, s2 = 0.f;
-    if (vec) {
-      for (int cv = threadIdx.x; cv < C / V; cv += blockDim.x) {
-        float fx[V], fd[V], fw[V];
-        vload16(xrow + cv * V, fx);
-        vload16(dyrow + cv * V, fd);
-        vload16(w + cv * V, fw);
-#pragma unroll
-        for (int q = 0; q < V; ++q) {
-          float dyg = fd[q] * fw[q];
-          s1 += dyg;
-          s2 = fmaf(dyg, (fx[q] - mu) * rs, s2);
-        }
-      }
-    } else {
-      for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float dyg = (float)dyrow[c] * (float)w[c];
-        float xhat = ((float)xrow[c] - mu) * rs;
-        s1 += dyg;
-        s2 = fmaf(dyg, xhat, s2);
-      }
-    }
-    float m1 = block_reduce_sum(s1, scratch) / C;
-    float m2 = block_reduce_sum(s2, scratch) / C;
-    if (vec) {
-      for (int cv = threadIdx.x; cv < C / V; cv += blockDim.x) {
-        float fx[V], fd[V], fw[V];
-        vload16(xrow + cv * V, fx);
-        vload16(dyrow + cv * V, fd);
-        vload16(w + cv * V, fw);
-#pragma unroll
-        for (int q = 0; q < V; ++q) {
-          float dyg = fd[q] * fw[q];
-          float xhat = (fx[q] - mu) * rs;
-          fd[q] = rs * (dyg - m1 - xhat * m2);
-        }
-        if (PLUS) {
-          float fp[V];
-          vload16(plus + (long long)r * C + cv * V, fp);
-#pragma unroll
-          for (int q = 0; q < V; ++q) fd[q] += fp[q];
-        }
-        vstore16(dxrow + cv * V, fd);
-      }
-    } else {
-      for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float dyg = (float)dyrow[c] * (float)w[c];
-        float xhat = ((float)xrow[c] - mu) * rs;
-        float v = rs * (dyg - m1 - xhat * m2);
-        if (PLUS) v += (float)plus[(long long)r * C + c];
-        dxrow[c] = (T)v;
-      }
-    }
-  }
-}
-
-// dgamma[c] = sum_r dy*xhat ; dbeta[c] = sum_r dy. Column reduction with
-// BOTH channel and row parallelism: a block covers 64 channels x 4 row
-// lanes (all 256 threads busy even at C=64), rows additionally split over
-// grid.y; 4-lane partials combine in LDS, then one atomicAdd per channel
-// chunk (dw/db zero-initialized by the caller). The previous
-// one-thread-per-channel form left ~3 blocks running on 256 CUs and was
-// 49% of the BERT step.
-template <typename T>
-__global__ void ln_bwd_dwdb_kernel(const T* __restrict__ x,
+// ---- LayerNorm / RMSNorm backward (dx) ----------------------------------------
+// dyg = dy*w, xhat = (x - mu) rstd (mu = 0 without MEAN);
+// MEAN:  dx = rstd * (dyg - mean(dyg) - xhat * mean(dyg*xhat))
+// else:  dx = rstd * (dyg - xhat * mean(dyg*xhat))
+// PLUS fuses the residual-stream gradient add (backward of the fused
+// z = x + res forward): dx += plus, saving the separate add pass.
+template <typename T, bool MEAN, bool PLUS>
+__global__ void norm_bwd_dx_kernel(const T* __restrict__ x,
                                    const T* __restrict__ dy,
+                                   const T* __restrict__ w,
                                    const float* __restrict__ mean,
                                    const float* __restrict__ rstd,
-                                   float* __restrict__ dw,
-                                   float* __restrict__ db, int R, int C,
-                                   int rows_per_block) {
-  __shared__ float sw[4][64], sb[4][64];
+                                   const T* __restrict__ plus,
+                                   T* __restrict__ dx, long long R, int C) {
+  __shared__ float scratch[kBlock / kWave];
+  using Row = NormRow<MEAN>;
+  for (Row r = blockIdx.x; r < (Row)R; r += gridDim.x) {
+    const long long base = (long long)r * C;
+    const T* xrow = x + base;
+    const T* dyrow = dy + base;
+    T* dxrow = dx + base;
+    const float rs = rstd[r];
+    float mu = 0.f;
+    if constexpr (MEAN) mu = mean[r];
+    auto hat = [&](float v) {
+      if constexpr (MEAN) return (v - mu) * rs;
+      else return v * rs;
+    };
+    float s1 = 0.f, s2 = 0.f;
+    row_walk<T>(C, [&](int c, auto width) {
+      constexpr int W = decltype(width)::value;
+      float fx[W], fd[W], fw[W];
+      vload<W>(xrow + c, fx);
+      vload<W>(dyrow + c, fd);
+      vload<W>(w + c, fw);
+#pragma unroll
+      for (int q = 0; q < W; ++q) {
+        float dyg = fd[q] * fw[q];
+        if constexpr (MEAN) s1 += dyg;
+        s2 = fmaf(dyg, hat(fx[q]), s2);
+      }
+    });
+    float m1 = 0.f;
+    if constexpr (MEAN) m1 = block_reduce_sum(s1, scratch) / C;
+    float m2 = block_reduce_sum(s2, scratch) / C;
+    row_walk<T>(C, [&](int c, auto width) {
+      constexpr int W = decltype(width)::value;
+      float fx[W], fd[W], fw[W];
+      vload<W>(xrow + c, fx);
+      vload<W>(dyrow + c, fd);
+      vload<W>(w + c, fw);
+#pragma unroll
+      for (int q = 0; q < W; ++q) {
+        float dyg = fd[q] * fw[q];
+        float xhat = hat(fx[q]);
+        if constexpr (MEAN) fd[q] = rs * (dyg - m1 - xhat * m2);
+        else fd[q] = rs * (dyg - xhat * m2);
+      }
+      if constexpr (PLUS) {
+        float fp[W];
+        vload<W>(plus + base + c, fp);
+#pragma unroll
+        for (int q = 0; q < W; ++q) fd[q] += fp[q];
+      }
+      vstore<W>(dxrow + c, fd);
+    });
+  }
+}
+
+// ---- column reductions -------------------------------------------------------
+// N per-channel sums over rows with BOTH channel and row parallelism: a block
+// covers 64 channels x 4 row lanes (all 256 threads busy even at C = 64),
+// rows additionally split over grid.y. term(r, c, acc) adds row r of channel
+// c to acc[0..N); the 4 lane partials combine in LDS, then one atomicAdd per
+// channel into out[i] (zero-initialized by the caller) or, with DIRECT and a
+// single row block, a plain store. The previous one-thread-per-channel form
+// left ~3 blocks running on 256 CUs and was 49% of the BERT step.
+template <int N, bool DIRECT, typename F>
+DEVINL void col_reduce_4x64(long long R, int C, int rows_per_block,
+                            float* const (&out)[N], F&& term) {
+  __shared__ float part[N][4][64];
   const int c_local = threadIdx.x & 63;
   const int row_lane = threadIdx.x >> 6;         // 0..3
   const int c = blockIdx.x * 64 + c_local;
   const long long r0 = (long long)blockIdx.y * rows_per_block;
-  const long long r1 = min(r0 + rows_per_block, (long long)R);
-  float acc_w = 0.f, acc_b = 0.f;
+  const long long r1 = min(r0 + rows_per_block, R);
+  float acc[N] = {};
   if (c < C) {
-    for (long long r = r0 + row_lane; r < r1; r += 4) {
-      float d = (float)dy[r * C + c];
-      float xhat = ((float)x[r * C + c] - mean[r]) * rstd[r];
-      acc_w = fmaf(d, xhat, acc_w);
-      acc_b += d;
-    }
+    for (long long r = r0 + row_lane; r < r1; r += 4) term(r, c, acc);
   }
-  sw[row_lane][c_local] = acc_w;
-  sb[row_lane][c_local] = acc_b;
+#pragma unroll
+  for (int i = 0; i < N; ++i) part[i][row_lane][c_local] = acc[i];
   __syncthreads();
   if (row_lane == 0 && c < C) {
-    float tw = sw[0][c_local] + sw[1][c_local] + sw[2][c_local] + sw[3][c_local];
-    float tb = sb[0][c_local] + sb[1][c_local] + sb[2][c_local] + sb[3][c_local];
-    if (gridDim.y == 1) {
-      dw[c] = tw;
-      db[c] = tb;
-    } else {
-      atomicAdd(&dw[c], tw);
-      atomicAdd(&db[c], tb);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      float t = part[i][0][c_local] + part[i][1][c_local] +
+                part[i][2][c_local] + part[i][3][c_local];
+      if (DIRECT && gridDim.y == 1) out[i][c] = t;
+      else atomicAdd(&out[i][c], t);
     }
+  }
+}
+
+// Vector form (C % 64 == 0, the ResNet case): each thread owns an 8-channel
+// run read as 16-B vectors (G13 — the 4 x 64 walk issues 2-B loads) and 32
+// row lanes stream rows r_begin, r_begin + 32, ... < r_end. The kernel walks
+// its rows into two 8-wide sums and puts them into row `lane` of its two
+// padded LDS tiles (from its own registers: handing the arrays to a helper
+// makes the compiler keep them as one vector and scalarize the packed
+// subtractions); col32x8_finish column-reduces the tiles with 64 threads,
+// then atomics. ~1.5x the 4 x 64 form at bench shapes.
+using Col32x8Tile = float[32][65];   // +1 pad: column reduce reads
+
+struct Col32x8 {
+  int lane, col;              // tile row (0..31) and first tile column (0..56)
+  int ch;                     // first of this thread's 8 channels
+  long long r_begin, r_end;
+};
+
+DEVINL Col32x8 col32x8_begin(long long M, int rows_per_block) {
+  const int c8 = threadIdx.x & 7;
+  const int rl = threadIdx.x >> 3;
+  const long long r0 = (long long)blockIdx.y * rows_per_block;
+  return {rl, c8 * 8, (int)(blockIdx.x * 64 + c8 * 8), r0 + rl,
+          min(r0 + rows_per_block, M)};
+}
+
+DEVINL void col32x8_finish(Col32x8Tile& l1, Col32x8Tile& l2,
+                           float* __restrict__ out1, float* __restrict__ out2) {
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    float t1 = 0.f, t2 = 0.f;
+#pragma unroll 8
+    for (int r = 0; r < 32; ++r) {
+      t1 += l1[r][threadIdx.x];
+      t2 += l2[r][threadIdx.x];
+    }
+    atomicAdd(&out1[blockIdx.x * 64 + threadIdx.x], t1);
+    atomicAdd(&out2[blockIdx.x * 64 + threadIdx.x], t2);
+  }
+}
+
+// dw[c] = sum_r dy*xhat; with MEAN (LayerNorm) also db[c] = sum_r dy.
+template <typename T, bool MEAN>
+__global__ void norm_bwd_dw_kernel(const T* __restrict__ x,
+                                   const T* __restrict__ dy,
+                                   const float* __restrict__ mean,
+                                   const float* __restrict__ rstd,
+                                   float* __restrict__ dw,
+                                   float* __restrict__ db, long long R, int C,
+                                   int rows_per_block) {
+  if constexpr (MEAN) {
+    float* const out[2] = {dw, db};
+    col_reduce_4x64<2, true>(
+        R, C, rows_per_block, out, [&](long long r, int c, float* acc) {
+          float d = (float)dy[r * C + c];
+          float xhat = ((float)x[r * C + c] - mean[r]) * rstd[r];
+          acc[0] = fmaf(d, xhat, acc[0]);
+          acc[1] += d;
+        });
+  } else {
+    float* const out[1] = {dw};
+    col_reduce_4x64<1, true>(
+        R, C, rows_per_block, out, [&](long long r, int c, float* acc) {
+          acc[0] = fmaf((float)dy[r * C + c], (float)x[r * C + c] * rstd[r],
+                        acc[0]);
+        });
   }
 }
 
@@ -218,87 +281,66 @@ template <typename T>
 __global__ void bn_stats_kernel(const T* __restrict__ x, float* __restrict__ sum,
                                 float* __restrict__ sumsq, long long M, int C,
                                 int rows_per_block) {
-  __shared__ float s1[4][64], s2[4][64];
-  const int c_local = threadIdx.x & 63;
-  const int row_lane = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + c_local;
-  const long long r0 = (long long)blockIdx.y * rows_per_block;
-  const long long r1 = min(r0 + rows_per_block, M);
-  float s = 0.f, ss = 0.f;
-  if (c < C) {
-    for (long long r = r0 + row_lane; r < r1; r += 4) {
-      float v = (float)x[r * C + c];
-      s += v;
-      ss = fmaf(v, v, ss);
-    }
-  }
-  s1[row_lane][c_local] = s;
-  s2[row_lane][c_local] = ss;
-  __syncthreads();
-  if (row_lane == 0 && c < C) {
-    atomicAdd(&sum[c], s1[0][c_local] + s1[1][c_local] + s1[2][c_local] + s1[3][c_local]);
-    atomicAdd(&sumsq[c], s2[0][c_local] + s2[1][c_local] + s2[2][c_local] + s2[3][c_local]);
-  }
+  float* const out[2] = {sum, sumsq};
+  col_reduce_4x64<2, false>(M, C, rows_per_block, out,
+                            [&](long long r, int c, float* acc) {
+                              float v = (float)x[r * C + c];
+                              acc[0] += v;
+                              acc[1] = fmaf(v, v, acc[1]);
+                            });
 }
 
-// Vectorized stats (C % 64 == 0, the ResNet case): each thread owns an
-// 8-channel 16-B run (G13 — the scalar walk above issues 2-B loads) and 32
-// row-lanes stream rows; partials meet in a padded LDS tile, 64 threads
-// column-reduce, then atomics. ~1.5x the scalar form at bench shapes.
 template <typename T>
 __global__ void bn_stats_vec_kernel(const T* __restrict__ x,
                                     float* __restrict__ sum,
                                     float* __restrict__ sumsq, long long M,
                                     int C, int rows_per_block) {
-  using VT = VecTraits<T>;
-  __shared__ float l1[32][65], l2[32][65];   // +1 pad: column reduce reads
-  const int c8 = threadIdx.x & 7;
-  const int rl = threadIdx.x >> 3;
-  const int ch = blockIdx.x * 64 + c8 * 8;
-  const long long r0 = (long long)blockIdx.y * rows_per_block;
-  const long long r1 = min(r0 + rows_per_block, M);
+  constexpr int V = VecTraits<T>::kElems;
+  __shared__ Col32x8Tile l1, l2;
+  const Col32x8 t = col32x8_begin(M, rows_per_block);
   float s[8] = {}, ss[8] = {};
-  for (long long r = r0 + rl; r < r1; r += 32) {
-    typename VT::VecT v =
-        *reinterpret_cast<const typename VT::VecT*>(&x[r * C + ch]);
-    float f[VT::kElems];
-    VT::to_float(v, f);
+  // fp32 (V == 4): the run is two vectors, each walked over the rows in turn
 #pragma unroll
-    for (int q = 0; q < VT::kElems; ++q) {
-      s[q] += f[q];
-      ss[q] = fmaf(f[q], f[q], ss[q]);
-    }
-  }
-  // f32 input: kElems == 4 — thread covers 8 channels in two vectors
-  if constexpr (VT::kElems == 4) {
-    typename VT::VecT v2;
-    for (long long r = r0 + rl; r < r1; r += 32) {
-      v2 = *reinterpret_cast<const typename VT::VecT*>(&x[r * C + ch + 4]);
-      float f[4];
-      VT::to_float(v2, f);
+  for (int part = 0; part < 8 / V; ++part) {
+    for (long long r = t.r_begin; r < t.r_end; r += 32) {
+      float f[V];
+      vload16(&x[r * C + t.ch + part * V], f);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        s[4 + q] += f[q];
-        ss[4 + q] = fmaf(f[q], f[q], ss[4 + q]);
+      for (int q = 0; q < V; ++q) {
+        s[part * V + q] += f[q];
+        ss[part * V + q] = fmaf(f[q], f[q], ss[part * V + q]);
       }
     }
   }
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
-    l1[rl][c8 * 8 + q] = s[q];
-    l2[rl][c8 * 8 + q] = ss[q];
+    l1[t.lane][t.col + q] = s[q];
+    l2[t.lane][t.col + q] = ss[q];
   }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    float t1 = 0.f, t2 = 0.f;
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) {
-      t1 += l1[r][threadIdx.x];
-      t2 += l2[r][threadIdx.x];
-    }
-    atomicAdd(&sum[blockIdx.x * 64 + threadIdx.x], t1);
-    atomicAdd(&sumsq[blockIdx.x * 64 + threadIdx.x], t2);
-  }
+  col32x8_finish(l1, l2, sum, sumsq);
+}
+
+// Backward pass 1: per-channel sum(dy) and sum(dy*xhat). With RELU, dy is
+// masked by (y > 0) first (y = the post-ReLU output, also masked in dx).
+template <typename T, bool RELU>
+__global__ void bn_bwd_stats_kernel(const T* __restrict__ x,
+                                    const T* __restrict__ dy,
+                                    const T* __restrict__ y_post,
+                                    const float* __restrict__ mean,
+                                    const float* __restrict__ rstd,
+                                    float* __restrict__ sum_dy,
+                                    float* __restrict__ sum_dyx, long long M,
+                                    int C, int rows_per_block) {
+  float* const out[2] = {sum_dy, sum_dyx};
+  col_reduce_4x64<2, false>(
+      M, C, rows_per_block, out, [&](long long r, int c, float* acc) {
+        const float mu = mean[c], rs = rstd[c];   // loop-invariant: hoisted
+        float d = (float)dy[r * C + c];
+        if (RELU) d = ((float)y_post[r * C + c] > 0.f) ? d : 0.f;
+        float xhat = ((float)x[r * C + c] - mu) * rs;
+        acc[0] += d;
+        acc[1] = fmaf(d, xhat, acc[1]);
+      });
 }
 
 template <typename T, bool RELU>
@@ -308,24 +350,20 @@ __global__ void bn_bwd_stats_vec_kernel(
     const float* __restrict__ rstd, float* __restrict__ sum_dy,
     float* __restrict__ sum_dyx, long long M, int C, int rows_per_block) {
   using VT = VecTraits<T>;
-  __shared__ float l1[32][65], l2[32][65];
-  const int c8 = threadIdx.x & 7;
-  const int rl = threadIdx.x >> 3;
-  const int ch = blockIdx.x * 64 + c8 * 8;
-  const long long r0 = (long long)blockIdx.y * rows_per_block;
-  const long long r1 = min(r0 + rows_per_block, M);
+  constexpr int V = VT::kElems;
+  __shared__ Col32x8Tile l1, l2;
+  const Col32x8 t = col32x8_begin(M, rows_per_block);
   float mu[8], rs[8];
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
-    mu[q] = mean[ch + q];
-    rs[q] = rstd[ch + q];
+    mu[q] = mean[t.ch + q];
+    rs[q] = rstd[t.ch + q];
   }
   float s1v[8] = {}, s2v[8] = {};
-  constexpr int V = VT::kElems;
-  for (long long r = r0 + rl; r < r1; r += 32) {
+  for (long long r = t.r_begin; r < t.r_end; r += 32) {
 #pragma unroll
     for (int part = 0; part < 8 / V; ++part) {
-      const long long base = r * C + ch + part * V;
+      const long long base = r * C + t.ch + part * V;
       float fx[V], fd[V], fy[V];
       typename VT::VecT vx =
           *reinterpret_cast<const typename VT::VecT*>(&x[base]);
@@ -351,20 +389,10 @@ __global__ void bn_bwd_stats_vec_kernel(
   }
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
-    l1[rl][c8 * 8 + q] = s1v[q];
-    l2[rl][c8 * 8 + q] = s2v[q];
+    l1[t.lane][t.col + q] = s1v[q];
+    l2[t.lane][t.col + q] = s2v[q];
   }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    float t1 = 0.f, t2 = 0.f;
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) {
-      t1 += l1[r][threadIdx.x];
-      t2 += l2[r][threadIdx.x];
-    }
-    atomicAdd(&sum_dy[blockIdx.x * 64 + threadIdx.x], t1);
-    atomicAdd(&sum_dyx[blockIdx.x * 64 + threadIdx.x], t2);
-  }
+  col32x8_finish(l1, l2, sum_dy, sum_dyx);
 }
 
 // Pass 2 (one small block over C): finalize mean/rstd, update running stats.
@@ -518,43 +546,6 @@ __global__ void bn_bwd_dx_vec_kernel(
   }
 }
 
-// Backward pass 1: per-channel sum(dy) and sum(dy*xhat). If RELU_FUSED, dy
-// is masked by (y > 0) first (y = the post-ReLU output, also masked in dx).
-template <typename T, bool RELU>
-__global__ void bn_bwd_stats_kernel(const T* __restrict__ x,
-                                    const T* __restrict__ dy,
-                                    const T* __restrict__ y_post,
-                                    const float* __restrict__ mean,
-                                    const float* __restrict__ rstd,
-                                    float* __restrict__ sum_dy,
-                                    float* __restrict__ sum_dyx, long long M,
-                                    int C, int rows_per_block) {
-  __shared__ float l1[4][64], l2[4][64];
-  const int c_local = threadIdx.x & 63;
-  const int row_lane = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + c_local;
-  const long long r0 = (long long)blockIdx.y * rows_per_block;
-  const long long r1 = min(r0 + rows_per_block, M);
-  float s1 = 0.f, s2 = 0.f;
-  if (c < C) {
-    const float mu = mean[c], rs = rstd[c];
-    for (long long r = r0 + row_lane; r < r1; r += 4) {
-      float d = (float)dy[r * C + c];
-      if (RELU) d = ((float)y_post[r * C + c] > 0.f) ? d : 0.f;
-      float xhat = ((float)x[r * C + c] - mu) * rs;
-      s1 += d;
-      s2 = fmaf(d, xhat, s2);
-    }
-  }
-  l1[row_lane][c_local] = s1;
-  l2[row_lane][c_local] = s2;
-  __syncthreads();
-  if (row_lane == 0 && c < C) {
-    atomicAdd(&sum_dy[c], l1[0][c_local] + l1[1][c_local] + l1[2][c_local] + l1[3][c_local]);
-    atomicAdd(&sum_dyx[c], l2[0][c_local] + l2[1][c_local] + l2[2][c_local] + l2[3][c_local]);
-  }
-}
-
 // Backward pass 2: dx = rstd*gamma*(dy - sum_dy/M - xhat*sum_dyx/M)
 template <typename T, bool RELU>
 __global__ void bn_bwd_dx_kernel(const T* __restrict__ x,
@@ -579,136 +570,77 @@ __global__ void bn_bwd_dx_kernel(const T* __restrict__ x,
   }
 }
 
-#define INST_BN(T)                                                              \
-  template __global__ void bn_stats_kernel<T>(const T*, float*, float*,         \
-                                              long long, int, int);             \
-  template __global__ void bn_norm_kernel<T, true>(                             \
-      const T*, const T*, const float*, const float*, const float*,             \
-      const float*, T*, long long, int);                                        \
-  template __global__ void bn_norm_kernel<T, false>(                            \
-      const T*, const T*, const float*, const float*, const float*,             \
-      const float*, T*, long long, int);                                        \
-  template __global__ void bn_norm_kernel<T, true, true>(                       \
-      const T*, const T*, const float*, const float*, const float*,             \
-      const float*, T*, long long, int);                                        \
-  template __global__ void bn_bwd_stats_kernel<T, true>(                        \
-      const T*, const T*, const T*, const float*, const float*, float*, float*, \
-      long long, int, int);                                                     \
-  template __global__ void bn_bwd_stats_kernel<T, false>(                       \
-      const T*, const T*, const T*, const float*, const float*, float*, float*, \
-      long long, int, int);                                                     \
-  template __global__ void bn_bwd_dx_kernel<T, true>(                           \
-      const T*, const T*, const T*, const float*, const float*, const float*,   \
-      const float*, const float*, T*, long long, int);                          \
-  template __global__ void bn_bwd_dx_kernel<T, false>(                          \
-      const T*, const T*, const T*, const float*, const float*, const float*,   \
-      const float*, const float*, T*, long long, int);
-
-INST_BN(float)
-INST_BN(bf16)
-
-#define INST_LN(T)                                                             \
-  template __global__ void ln_fwd_kernel<T, false>(                            \
-      const T*, const T*, const T*, const T*, T*, T*, float*, float*, int,     \
-      int, float);                                                             \
-  template __global__ void ln_fwd_kernel<T, true>(                             \
-      const T*, const T*, const T*, const T*, T*, T*, float*, float*, int,     \
-      int, float);                                                             \
-  template __global__ void ln_bwd_dx_kernel<T, false>(                         \
-      const T*, const T*, const T*, const float*, const float*, const T*, T*,  \
-      int, int);                                                               \
-  template __global__ void ln_bwd_dx_kernel<T, true>(                          \
-      const T*, const T*, const T*, const float*, const float*, const T*, T*,  \
-      int, int);                                                               \
-  template __global__ void ln_bwd_dwdb_kernel<T>(const T*, const T*,           \
-                                                 const float*, const float*,   \
-                                                 float*, float*, int, int,     \
-                                                 int);
-
-INST_LN(float)
-INST_LN(bf16)
-
 // ---- launchers -------------------------------------------------------------
 #include "launchers.h"
 
-static int row_grid(long long rows) { return rows < kMaxGrid ? (int)rows : kMaxGrid; }
+// dtype x mode dispatch: calls f(TypeTag<T>, integral_constant<int, mode>)
+// for T = bf16 / float and mode in [0, N), so each launcher names its kernel
+// once and only the listed modes are instantiated.
+template <typename T>
+struct TypeTag { using type = T; };
 
-void launch_ln_fwd(bool is_bf16, const void* x, const void* res, const void* w,
-                   const void* b, void* y, void* zout, float* mean,
-                   float* rstd, int R, int C, float eps, hipStream_t s) {
-  #define LNF_CALL(T, A)                                                      \
-    hipLaunchKernelGGL((ln_fwd_kernel<T, A>), dim3(row_grid(R)),              \
-                       dim3(kBlock), 0, s, (const T*)x, (const T*)res,        \
-                       (const T*)w, (const T*)b, (T*)y, (T*)zout, mean, rstd, \
-                       R, C, eps)
-  if (is_bf16) { if (res) LNF_CALL(bf16, true); else LNF_CALL(bf16, false); }
-  else { if (res) LNF_CALL(float, true); else LNF_CALL(float, false); }
-  #undef LNF_CALL
-}
-
-void launch_ln_bwd_dx(bool is_bf16, const void* x, const void* dy, const void* w,
-                      const float* mean, const float* rstd, const void* plus,
-                      void* dx, int R, int C, hipStream_t s) {
-  #define LNB_CALL(T, P)                                                      \
-    hipLaunchKernelGGL((ln_bwd_dx_kernel<T, P>), dim3(row_grid(R)),           \
-                       dim3(kBlock), 0, s, (const T*)x, (const T*)dy,         \
-                       (const T*)w, mean, rstd, (const T*)plus, (T*)dx, R, C)
-  if (is_bf16) { if (plus) LNB_CALL(bf16, true); else LNB_CALL(bf16, false); }
-  else { if (plus) LNB_CALL(float, true); else LNB_CALL(float, false); }
-  #undef LNB_CALL
-}
-
-void launch_ln_bwd_dwdb(bool is_bf16, const void* x, const void* dy,
-                        const float* mean, const float* rstd, float* dw,
-                        float* db, int R, int C, hipStream_t s) {
-  const int cgrid = (C + 63) / 64;
-  int target = 1024 / (cgrid > 0 ? cgrid : 1);
-  if (target < 1) target = 1;
-  int rpb = (R + target - 1) / target;
-  if (rpb < 128) rpb = 128;
-  int gy = (R + rpb - 1) / rpb;
-  dim3 grid(cgrid, gy);
-  if (is_bf16)
-    hipLaunchKernelGGL(ln_bwd_dwdb_kernel<bf16>, grid, dim3(kBlock), 0, s,
-                       (const bf16*)x, (const bf16*)dy, mean, rstd, dw, db, R,
-                       C, rpb);
-  else
-    hipLaunchKernelGGL(ln_bwd_dwdb_kernel<float>, grid, dim3(kBlock), 0,
-                       s, (const float*)x, (const float*)dy, mean, rstd, dw, db,
-                       R, C, rpb);
-}
-
-// rows_per_block tuned so grid.y gives ~8 blocks/CU worth of parallelism
-static void bn_rows_split(long long M, int C, int* rows_per_block, int* grid_y) {
-  int col_blocks = (C + 63) / 64;
-  long long target_blocks = 2048 / (col_blocks > 0 ? col_blocks : 1);
-  if (target_blocks < 1) target_blocks = 1;
-  long long rpb = (M + target_blocks - 1) / target_blocks;
-  if (rpb < 64) rpb = 64;
-  *rows_per_block = (int)rpb;
-  *grid_y = (int)((M + rpb - 1) / rpb);
-}
-
-void launch_bn_stats(bool is_bf16, const void* x, float* sum, float* sumsq,
-                     long long M, int C, hipStream_t s) {
-  int rpb, gy;
-  bn_rows_split(M, C, &rpb, &gy);
-  dim3 grid((C + 63) / 64, gy);
-  if ((C % 64) == 0) {   // vectorized 16-B path (every ResNet BN width)
-    if (is_bf16)
-      hipLaunchKernelGGL(bn_stats_vec_kernel<bf16>, grid, dim3(kBlock), 0, s,
-                         (const bf16*)x, sum, sumsq, M, C, rpb);
-    else
-      hipLaunchKernelGGL(bn_stats_vec_kernel<float>, grid, dim3(kBlock), 0, s,
-                         (const float*)x, sum, sumsq, M, C, rpb);
-    return;
+template <typename T, int N, typename F>
+static void dispatch_mode(int mode, F&& f) {
+  if constexpr (N > 0) {
+    if (mode == N - 1) f(TypeTag<T>{}, std::integral_constant<int, N - 1>{});
+    else dispatch_mode<T, N - 1>(mode, f);
   }
-  if (is_bf16)
-    hipLaunchKernelGGL(bn_stats_kernel<bf16>, grid, dim3(kBlock), 0, s,
-                       (const bf16*)x, sum, sumsq, M, C, rpb);
-  else
-    hipLaunchKernelGGL(bn_stats_kernel<float>, grid, dim3(kBlock), 0, s,
-                       (const float*)x, sum, sumsq, M, C, rpb);
+}
+
+template <int N, typename F>
+static void norm_dispatch(bool is_bf16, int mode, F&& f) {
+  if (is_bf16) dispatch_mode<bf16, N>(mode, f);
+  else dispatch_mode<float, N>(mode, f);
+}
+
+// mode bit 1 = MEAN (LayerNorm), bit 0 = ADD / PLUS
+void launch_norm_fwd(const NormRowRoute& rt, bool is_bf16, bool center,
+                     const void* x, const void* res, const void* w,
+                     const void* b, void* y, void* zout, float* mean,
+                     float* rstd, long long R, int C, float eps,
+                     hipStream_t s) {
+  norm_dispatch<4>(is_bf16, (center ? 2 : 0) + (res ? 1 : 0), [&](auto t, auto m) {
+    using T = typename decltype(t)::type;
+    constexpr int mode = decltype(m)::value;
+    hipLaunchKernelGGL((norm_fwd_kernel<T, (mode & 2) != 0, (mode & 1) != 0>),
+                       dim3(rt.grid), dim3(kBlock), 0, s, (const T*)x,
+                       (const T*)res, (const T*)w, (const T*)b, (T*)y, (T*)zout,
+                       mean, rstd, R, C, eps);
+  });
+}
+
+void launch_norm_bwd(const NormRowRoute& rt, bool is_bf16, bool center,
+                     const void* x, const void* dy, const void* w,
+                     const float* mean, const float* rstd, const void* plus,
+                     void* dx, float* dw, float* db, long long R, int C,
+                     hipStream_t s) {
+  norm_dispatch<4>(is_bf16, (center ? 2 : 0) + (plus ? 1 : 0), [&](auto t, auto m) {
+    using T = typename decltype(t)::type;
+    constexpr int mode = decltype(m)::value;
+    constexpr bool MEAN = (mode & 2) != 0;
+    hipLaunchKernelGGL((norm_bwd_dx_kernel<T, MEAN, (mode & 1) != 0>),
+                       dim3(rt.grid), dim3(kBlock), 0, s, (const T*)x,
+                       (const T*)dy, (const T*)w, mean, rstd, (const T*)plus,
+                       (T*)dx, R, C);
+    hipLaunchKernelGGL((norm_bwd_dw_kernel<T, MEAN>),
+                       dim3(rt.chunks, rt.grid_y), dim3(kBlock), 0, s,
+                       (const T*)x, (const T*)dy, mean, rstd, dw, db, R, C,
+                       rt.rows_per_block);
+  });
+}
+
+void launch_bn_stats(const BnRoute& rt, bool is_bf16, const void* x, float* sum,
+                     float* sumsq, long long M, int C, hipStream_t s) {
+  const dim3 grid(rt.chunks, rt.grid_y);
+  norm_dispatch<1>(is_bf16, 0, [&](auto t, auto) {
+    using T = typename decltype(t)::type;
+    if (rt.stats_vec)   // 16-B path (every ResNet BN width)
+      hipLaunchKernelGGL(bn_stats_vec_kernel<T>, grid, dim3(kBlock), 0, s,
+                         (const T*)x, sum, sumsq, M, C, rt.rows_per_block);
+    else
+      hipLaunchKernelGGL(bn_stats_kernel<T>, grid, dim3(kBlock), 0, s,
+                         (const T*)x, sum, sumsq, M, C, rt.rows_per_block);
+  });
 }
 
 void launch_bn_finalize(const float* sum, const float* sumsq, float* mean,
@@ -720,103 +652,64 @@ void launch_bn_finalize(const float* sum, const float* sumsq, float* mean,
                      running_var, M, C, eps, momentum);
 }
 
-void launch_bn_norm(bool is_bf16, bool relu, const void* x, const void* res,
-                    const float* mean, const float* rstd, const float* gamma,
-                    const float* beta, void* y, long long M, int C,
-                    hipStream_t s) {
-  const int grid = elementwise_grid(M * C / 4 + 1);
-  const int velems = is_bf16 ? 8 : 4;
-  if ((C % velems) == 0 && C <= 6144) {   // vectorized + LDS constants
-    const size_t smem = 2u * C * sizeof(float);
-    #define BN_NV(T, R, A)                                                   \
-      hipLaunchKernelGGL((bn_norm_vec_kernel<T, R, A>), dim3(grid),          \
-                         dim3(kBlock), smem, s, (const T*)x, (const T*)res,  \
-                         mean, rstd, gamma, beta, (T*)y, M, C)
-    if (is_bf16) {
-      if (res) BN_NV(bf16, true, true);
-      else if (relu) BN_NV(bf16, true, false);
-      else BN_NV(bf16, false, false);
-    } else {
-      if (res) BN_NV(float, true, true);
-      else if (relu) BN_NV(float, true, false);
-      else BN_NV(float, false, false);
-    }
-    #undef BN_NV
-    return;
-  }
-  #define BN_NORM(T, R, A)                                                  \
-    hipLaunchKernelGGL((bn_norm_kernel<T, R, A>), dim3(grid), dim3(kBlock), \
-                       0, s, (const T*)x, (const T*)res, mean, rstd, gamma, \
-                       beta, (T*)y, M, C)
-  if (is_bf16) {
-    if (res) BN_NORM(bf16, true, true);
-    else if (relu) BN_NORM(bf16, true, false);
-    else BN_NORM(bf16, false, false);
-  } else {
-    if (res) BN_NORM(float, true, true);
-    else if (relu) BN_NORM(float, true, false);
-    else BN_NORM(float, false, false);
-  }
-  #undef BN_NORM
+// mode 0 plain, 1 fused ReLU, 2 fused residual add + ReLU
+void launch_bn_norm(const BnRoute& rt, bool is_bf16, bool relu, const void* x,
+                    const void* res, const float* mean, const float* rstd,
+                    const float* gamma, const float* beta, void* y, long long M,
+                    int C, hipStream_t s) {
+  norm_dispatch<3>(is_bf16, res ? 2 : relu ? 1 : 0, [&](auto t, auto m) {
+    using T = typename decltype(t)::type;
+    constexpr bool RELU = decltype(m)::value >= 1, ADDIN = decltype(m)::value == 2;
+    if (rt.norm_vec)   // 16-B vectors + LDS constants
+      hipLaunchKernelGGL((bn_norm_vec_kernel<T, RELU, ADDIN>),
+                         dim3(rt.elem_grid), dim3(kBlock), rt.norm_lds, s,
+                         (const T*)x, (const T*)res, mean, rstd, gamma, beta,
+                         (T*)y, M, C);
+    else
+      hipLaunchKernelGGL((bn_norm_kernel<T, RELU, ADDIN>), dim3(rt.elem_grid),
+                         dim3(kBlock), 0, s, (const T*)x, (const T*)res, mean,
+                         rstd, gamma, beta, (T*)y, M, C);
+  });
 }
 
-void launch_bn_bwd_stats(bool is_bf16, bool relu, const void* x, const void* dy,
-                         const void* y_post, const float* mean,
-                         const float* rstd, float* sum_dy, float* sum_dyx,
-                         long long M, int C, hipStream_t s) {
-  int rpb, gy;
-  bn_rows_split(M, C, &rpb, &gy);
-  dim3 grid((C + 63) / 64, gy);
-  if ((C % 64) == 0) {   // vectorized 16-B path
-    #define BN_BSV(T, R)                                                       \
-      hipLaunchKernelGGL((bn_bwd_stats_vec_kernel<T, R>), grid, dim3(kBlock), \
-                         0, s, (const T*)x, (const T*)dy, (const T*)y_post,   \
-                         mean, rstd, sum_dy, sum_dyx, M, C, rpb)
-    if (is_bf16) { if (relu) BN_BSV(bf16, true); else BN_BSV(bf16, false); }
-    else { if (relu) BN_BSV(float, true); else BN_BSV(float, false); }
-    #undef BN_BSV
-    return;
-  }
-  #define BN_BS(T, R)                                                        \
-    hipLaunchKernelGGL((bn_bwd_stats_kernel<T, R>), grid, dim3(kBlock), 0, s, \
-                       (const T*)x, (const T*)dy, (const T*)y_post, mean,     \
-                       rstd, sum_dy, sum_dyx, M, C, rpb)
-  if (is_bf16) { if (relu) BN_BS(bf16, true); else BN_BS(bf16, false); }
-  else { if (relu) BN_BS(float, true); else BN_BS(float, false); }
-  #undef BN_BS
+void launch_bn_bwd_stats(const BnRoute& rt, bool is_bf16, bool relu,
+                         const void* x, const void* dy, const void* y_post,
+                         const float* mean, const float* rstd, float* sum_dy,
+                         float* sum_dyx, long long M, int C, hipStream_t s) {
+  const dim3 grid(rt.chunks, rt.grid_y);
+  norm_dispatch<2>(is_bf16, relu ? 1 : 0, [&](auto t, auto m) {
+    using T = typename decltype(t)::type;
+    constexpr bool RELU = decltype(m)::value == 1;
+    if (rt.stats_vec)
+      hipLaunchKernelGGL((bn_bwd_stats_vec_kernel<T, RELU>), grid, dim3(kBlock),
+                         0, s, (const T*)x, (const T*)dy, (const T*)y_post,
+                         mean, rstd, sum_dy, sum_dyx, M, C, rt.rows_per_block);
+    else
+      hipLaunchKernelGGL((bn_bwd_stats_kernel<T, RELU>), grid, dim3(kBlock), 0,
+                         s, (const T*)x, (const T*)dy, (const T*)y_post, mean,
+                         rstd, sum_dy, sum_dyx, M, C, rt.rows_per_block);
+  });
 }
 
-void launch_bn_bwd_dx(bool is_bf16, bool relu, const void* x, const void* dy,
-                      const void* y_post, const float* mean, const float* rstd,
-                      const float* gamma, const float* sum_dy,
-                      const float* sum_dyx, void* dx, void* dres, long long M,
-                      int C, hipStream_t s) {
-  const int grid = elementwise_grid(M * C / 4 + 1);
-  const int velems = is_bf16 ? 8 : 4;
-  if ((C % velems) == 0 && C <= 4096) {   // vectorized + LDS constants
-    const size_t smem = 3u * C * sizeof(float);
-    #define BN_DXV(T, R, D)                                                   \
-      hipLaunchKernelGGL((bn_bwd_dx_vec_kernel<T, R, D>), dim3(grid),         \
-                         dim3(kBlock), smem, s, (const T*)x, (const T*)dy,    \
-                         (const T*)y_post, mean, rstd, gamma, sum_dy,         \
-                         sum_dyx, (T*)dx, (T*)dres, M, C)
-    if (is_bf16) {
-      if (dres) BN_DXV(bf16, true, true);
-      else if (relu) BN_DXV(bf16, true, false);
-      else BN_DXV(bf16, false, false);
-    } else {
-      if (dres) BN_DXV(float, true, true);
-      else if (relu) BN_DXV(float, true, false);
-      else BN_DXV(float, false, false);
-    }
-    #undef BN_DXV
-    return;
-  }
-  #define BN_DX(T, R)                                                       \
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<T, R>), dim3(grid), dim3(kBlock),  \
-                       0, s, (const T*)x, (const T*)dy, (const T*)y_post,   \
-                       mean, rstd, gamma, sum_dy, sum_dyx, (T*)dx, M, C)
-  if (is_bf16) { if (relu) BN_DX(bf16, true); else BN_DX(bf16, false); }
-  else { if (relu) BN_DX(float, true); else BN_DX(float, false); }
-  #undef BN_DX
+// mode 0 plain, 1 ReLU-masked, 2 ReLU-masked + dres (vector pass only:
+// rt.dres_ok, which bindings.cpp refuses without)
+void launch_bn_bwd_dx(const BnRoute& rt, bool is_bf16, bool relu, const void* x,
+                      const void* dy, const void* y_post, const float* mean,
+                      const float* rstd, const float* gamma,
+                      const float* sum_dy, const float* sum_dyx, void* dx,
+                      void* dres, long long M, int C, hipStream_t s) {
+  norm_dispatch<3>(is_bf16, dres ? 2 : relu ? 1 : 0, [&](auto t, auto m) {
+    using T = typename decltype(t)::type;
+    constexpr bool RELU = decltype(m)::value >= 1, DRES = decltype(m)::value == 2;
+    if (rt.dx_vec)   // 16-B vectors + LDS constants
+      hipLaunchKernelGGL((bn_bwd_dx_vec_kernel<T, RELU, DRES>),
+                         dim3(rt.elem_grid), dim3(kBlock), rt.dx_lds, s,
+                         (const T*)x, (const T*)dy, (const T*)y_post, mean, rstd,
+                         gamma, sum_dy, sum_dyx, (T*)dx, (T*)dres, M, C);
+    else
+      hipLaunchKernelGGL((bn_bwd_dx_kernel<T, RELU>), dim3(rt.elem_grid),
+                         dim3(kBlock), 0, s, (const T*)x, (const T*)dy,
+                         (const T*)y_post, mean, rstd, gamma, sum_dy, sum_dyx,
+                         (T*)dx, M, C);
+  });
 }

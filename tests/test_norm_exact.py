@@ -1,7 +1,8 @@
-"""LayerNorm / BatchNorm (norm.hip) and RMSNorm (llama_ops.hip) on every
-route, bf16 and fp32, against float64 built from the stored inputs, with
-elementwise bounds derived from the arithmetic (the form of
-tests/test_softmax_exact.py). The route each case takes is asserted first.
+"""LayerNorm, RMSNorm and BatchNorm (norm.hip) on every route, bf16 and
+fp32, against float64 built from the stored inputs, with elementwise bounds
+derived from the arithmetic (the form of tests/test_softmax_exact.py). The
+route each case takes is asserted first: on the GPU what norm_route (the
+csrc/norm_route.h the launchers execute) returns, against the tables below.
 
 Notation: e = 2^-24 (one fp32 rounding), u = 2^-8 for a round-to-nearest bf16
 store and 0 for fp32, n the number of summed terms (C for a LayerNorm /
@@ -147,7 +148,9 @@ def vec_width(dt):
     return 8 if dt == BF16 else 4
 
 
-# ---- routes: mirrors of the launchers' gates (the source of truth) -----------
+# ---- routes: the CPU emulation's model of csrc/norm_route.h -------------------
+# The GPU tests assert the tables below against norm_route itself;
+# tests/test_norm_route.py holds these two functions equal to it.
 
 def route_rows(R, C, dtype):
     """LayerNorm / RMSNorm. Row kernels: 16-byte vectors iff C % V == 0, 256
@@ -268,18 +271,33 @@ def case_id(c):
     return f"{c[0]}x{c[1]}_{dname(c[2])}"
 
 
-def check_route_rows(R, C, dtype):
+ROW_KEYS = ("vec", "trips", "capped", "rows_per_block", "grid_y")
+BN_KEYS = ("stats", "rows_per_block", "grid_y", "norm", "norm_trips", "dx",
+           "dx_trips")
+
+
+def launched_route(family, rows, C, dtype):
+    """What the launchers execute, in the order of route_rows / route_bn."""
+    d = OPS.norm_route(family, rows, C, dtype == BF16)
+    return tuple(d[k] for k in (BN_KEYS if family == "bn" else ROW_KEYS))
+
+
+def check_route_rows(R, C, dtype, family=None):
+    """The table against the launchers' route (family given: GPU) or against
+    the Python model."""
     per, capped, rpb, gy = ROW_SHAPES[(R, C)]
     want = per[dtype] + (capped, rpb, gy)
-    got = route_rows(R, C, dtype)
+    got = launched_route(family, R, C, dtype) if family \
+        else route_rows(R, C, dtype)
     assert got == want, (R, C, dname(dtype), got, want)
 
 
-def check_route_bn(M, C, dtype):
+def check_route_bn(M, C, dtype, launched=False):
     per, stats, rpb, gy, _ = BN_SHAPES[(M, C)]
     n, nt, d, dt = per[dtype]
     want = (stats, rpb, gy, n, nt, d, dt)
-    got = route_bn(M, C, dtype)
+    got = launched_route("bn", M, C, dtype) if launched \
+        else route_bn(M, C, dtype)
     assert got == want, (M, C, dname(dtype), got, want)
 
 
@@ -614,7 +632,7 @@ class Gpu:
 @pytest.mark.gpu
 @pytest.mark.parametrize("c", ROW_CASES, ids=case_id)
 def test_layernorm(c):
-    check_route_rows(*c)
+    check_route_rows(*c, family="ln")
     r = run_rows(Gpu, "ln", *c)
     report("layernorm " + case_id(c), r)
     assert_within("layernorm " + case_id(c), r)
@@ -623,7 +641,7 @@ def test_layernorm(c):
 @pytest.mark.gpu
 @pytest.mark.parametrize("c", ROW_CASES, ids=case_id)
 def test_rmsnorm(c):
-    check_route_rows(*c)
+    check_route_rows(*c, family="rms")
     r = run_rows(Gpu, "rms", *c)
     report("rmsnorm " + case_id(c), r)
     assert_within("rmsnorm " + case_id(c), r)
@@ -632,7 +650,7 @@ def test_rmsnorm(c):
 @pytest.mark.gpu
 @pytest.mark.parametrize("c", BN_CASES, ids=case_id)
 def test_batchnorm(c):
-    check_route_bn(*c)
+    check_route_bn(*c, launched=True)
     r = run_bn(Gpu, *c)
     report("batchnorm " + case_id(c), r)
     assert_within("batchnorm " + case_id(c), r)
@@ -645,7 +663,7 @@ def test_batchnorm_eval(shape, dtype):
     """bn_fwd_eval normalizes with the given statistics: they are exact
     inputs, so only the rounding terms of the bound remain."""
     M, C = shape
-    check_route_bn(M, C, dtype)
+    check_route_bn(M, C, dtype, launched=True)
     x, _, _, gamma, beta, rm0, rv0 = bn_inputs(M, C, dtype)
     rstd = (rv0 + EPS).rsqrt()
     r = {}

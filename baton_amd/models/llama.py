@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
@@ -107,7 +107,7 @@ class LlamaAttention(nn.Module):
         self.v_proj = LoRALinear(cfg.hidden, kv_dim, cfg.lora_rank, cfg.lora_alpha)
         self.o_proj = LoRALinear(cfg.hidden, cfg.hidden, cfg.lora_rank, cfg.lora_alpha)
 
-    def forward(self, x, cos_t, sin_t):
+    def forward(self, x, cos_t, sin_t, seq_lens=None):
         B, S, H = x.shape
         cfg = self.cfg
         dh = self.head_dim
@@ -119,7 +119,8 @@ class LlamaAttention(nn.Module):
         # GQA: KV heads stay un-replicated AND un-permuted — the strided
         # batched GEMM consumes [B,S,h,dh] views in place (b_group indexes
         # the shared KV head in-kernel; no repeat_interleave, no permutes)
-        o = BF.attention_bshd(q, k, v, causal=True)          # [B, S, h, dh]
+        o = BF.attention_bshd(q, k, v, causal=True,
+                              seq_lens=seq_lens)             # [B, S, h, dh]
         return self.o_proj(o.reshape(B, S, H))
 
 
@@ -152,7 +153,7 @@ class LlamaDecoderLayer(nn.Module):
         self.mlp_norm = RMSNorm(cfg.hidden, cfg.rms_eps)
         self.mlp = LlamaMLP(cfg)
 
-    def forward(self, x, pend, cos_t, sin_t):
+    def forward(self, x, pend, cos_t, sin_t, seq_lens=None):
         """Pending-pair form: the true residual stream is x (+ pend).
         Each norm consumes the pending add via the fused add_rms_norm
         kernel (one pass writes z = x + pend and normalizes it), so NO
@@ -163,7 +164,7 @@ class LlamaDecoderLayer(nn.Module):
         else:
             n1, z1 = BF.add_rms_norm(x, pend, self.attn_norm.weight,
                                      self.attn_norm.eps)
-        a = self.attn(n1, cos_t, sin_t)
+        a = self.attn(n1, cos_t, sin_t, seq_lens)
         n2, z2 = BF.add_rms_norm(z1, a, self.mlp_norm.weight,
                                  self.mlp_norm.eps)
         return z2, self.mlp(n2)
@@ -171,13 +172,39 @@ class LlamaDecoderLayer(nn.Module):
 
 class LlamaForCausalLM(nn.Module):
     """Causal LM fine-tune: next-token CE. Embeddings + lm_head frozen
-    (the LoRA setup trains adapters only)."""
+    (the LoRA setup trains adapters only).
+
+    Padded batches and masked prompts: construct the model with
+    ``ignore_index`` (-100 is what tokenizer pipelines write) and put that
+    value into the labels of every position that is not to be scored; ``lm_loss``
+    then averages over the scored positions only (``BF.cross_entropy`` with
+    ``ignore_index``; an all-ignored minibatch has loss 0). Validate labels
+    when the data is prepared (``BF.validate_labels``). ``ignore_index=None``
+    is the dense loss: every label must be a class and every position is
+    scored.
+
+    ``forward(input_ids, seq_lens)`` takes the live lengths of a right-padded
+    batch (int32 [B] on the ids' device) and hands them to the causal flash
+    attention; ``train_round(ids, seq_lens, labels)`` trains on such data
+    (LocalTrainer calls ``model(ids, seq_lens)``; that path runs eagerly).
+    What each of the two buys, stated plainly: under a causal mask with right
+    padding a live query never sees a padded key, so the hidden states and
+    the adapter gradients at live positions are the same with and without
+    ``seq_lens``. Ignoring the labels is what makes the training *correct*;
+    ``seq_lens`` only buys skipped padded tiles and zero-filled padded
+    attention rows. profiles/r05_flash_varlen.md measured 0.59x of the dense
+    flash time at S = 512 with half lengths; what that is worth for a whole
+    Llama step is unmeasured. The lm_head GEMM still computes the ignored
+    rows: compacting them needs a host-visible count and is not done."""
 
     name = "llama-lora"
 
-    def __init__(self, cfg: LlamaConfig, train_config: Optional[TrainConfig] = None):
+    def __init__(self, cfg: LlamaConfig,
+                 train_config: Optional[TrainConfig] = None,
+                 ignore_index: Optional[int] = None):
         super().__init__()
         self.cfg = cfg
+        self.ignore_index = ignore_index
         self.embed = nn.Embedding(cfg.vocab_size, cfg.hidden)
         self.embed.weight.requires_grad_(False)
         self.layers = nn.ModuleList(LlamaDecoderLayer(cfg) for _ in range(cfg.layers))
@@ -191,14 +218,17 @@ class LlamaForCausalLM(nn.Module):
         tc = train_config or TrainConfig(optimizer="adam", lr=1e-4)
         self._trainer = LocalTrainer(tc, loss_fn=self.lm_loss)
 
-    def forward(self, input_ids: torch.Tensor) -> torch.Tensor:
+    def forward(self, input_ids: torch.Tensor,
+                seq_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
         S = input_ids.shape[1]
         x = self.embed(input_ids)
         cos = self.rope_cos[:S].contiguous()
         sin = self.rope_sin[:S].contiguous()
+        if seq_lens is not None:
+            seq_lens = seq_lens.to(torch.int32).contiguous()
         pend = None
         for layer in self.layers:
-            x, pend = layer(x, pend, cos, sin)
+            x, pend = layer(x, pend, cos, sin, seq_lens)
         if pend is None:
             return self.final_norm(x)
         y, _ = BF.add_rms_norm(x, pend, self.final_norm.weight,
@@ -207,11 +237,13 @@ class LlamaForCausalLM(nn.Module):
 
     def lm_loss(self, hidden: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         """Next-token CE: hidden [B,S,H], labels [B,S] (input shifted by
-        caller or identical ids — we shift internally)."""
+        caller or identical ids — we shift internally). Positions whose
+        label is ``self.ignore_index`` (when set) are not scored."""
         B, S, H = hidden.shape
         logits = self.lm_head(hidden[:, :-1, :].reshape(-1, H).contiguous())
         targets = labels[:, 1:].reshape(-1).contiguous()
-        return BF.cross_entropy(logits.contiguous(), targets)
+        return BF.cross_entropy(logits.contiguous(), targets,
+                                self.ignore_index)
 
     def train_round(self, *data, n_epoch: int = 1) -> List[float]:
         return self._trainer(self, data, n_epoch)
@@ -230,12 +262,28 @@ class LlamaForCausalLM(nn.Module):
 
 
 def llama_lora(cfg: Optional[LlamaConfig] = None,
-               train_config: Optional[TrainConfig] = None) -> LlamaForCausalLM:
-    return LlamaForCausalLM(cfg or llama3_8b_config(), train_config)
+               train_config: Optional[TrainConfig] = None,
+               ignore_index: Optional[int] = None) -> LlamaForCausalLM:
+    return LlamaForCausalLM(cfg or llama3_8b_config(), train_config,
+                            ignore_index)
+
+
+PAD_ID = 0   # pad token of make_synthetic_clm(var_len=True)
 
 
 def make_synthetic_clm(n_samples: int, seq_len: int, vocab_size: int,
-                       seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+                       seed: int = 0, var_len: bool = False):
+    """Synthetic causal-LM data: random ids, labels = ids (``lm_loss``
+    shifts). ``var_len=True`` returns ``(ids, seq_lens, labels)`` instead:
+    lengths drawn uniformly in [2, seq_len] (int32 [n]; 2 so that every
+    sample scores at least one next token), live positions with
+    ``labels = ids``, and in the padded positions ``PAD_ID`` ids and -100
+    labels, for a model built with ``ignore_index=-100``."""
     g = torch.Generator().manual_seed(seed)
     ids = torch.randint(0, vocab_size, (n_samples, seq_len), generator=g)
-    return ids, ids.clone()
+    if not var_len:
+        return ids, ids.clone()
+    lens = torch.randint(2, seq_len + 1, (n_samples,), generator=g)
+    live = torch.arange(seq_len)[None, :] < lens[:, None]
+    labels = ids.masked_fill(~live, -100)
+    return ids.masked_fill(~live, PAD_ID), lens.to(torch.int32), labels

@@ -259,6 +259,76 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
   return dx;
 }
 
+// Cross-entropy with ignored labels (loss.hip, MASKED). Everything is refused
+// here, by argument name, before anything is allocated or launched; what the
+// labels hold is the kernels' business (they skip what is not a class).
+static void check_ce_masked(const char* op, const at::Tensor& logits,
+                            const at::Tensor& target) {
+  TORCH_CHECK(logits.is_cuda(), op, ": logits must be on the GPU");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat ||
+                  logits.scalar_type() == at::kBFloat16,
+              op, ": logits must be fp32 or bf16");
+  TORCH_CHECK(logits.dim() == 2, op, ": logits must be 2-D [B, C], got ",
+              logits.dim(), "-D");
+  TORCH_CHECK(logits.is_contiguous(), op, ": logits must be contiguous");
+  TORCH_CHECK(logits.size(0) > 0 && logits.size(1) > 0, op,
+              ": logits must not be empty, got [", logits.size(0), ", ",
+              logits.size(1), "]");
+  TORCH_CHECK(logits.size(0) <= std::numeric_limits<int>::max() &&
+                  logits.size(1) <= std::numeric_limits<int>::max(),
+              op, ": logits [", logits.size(0), ", ", logits.size(1),
+              "] exceeds the int row / class index of the kernels");
+  TORCH_CHECK(target.scalar_type() == at::kLong, op, ": target must be int64");
+  TORCH_CHECK(target.is_contiguous(), op, ": target must be contiguous");
+  TORCH_CHECK(target.device() == logits.device(), op,
+              ": target must be on the logits' device");
+  TORCH_CHECK(target.numel() == logits.size(0), op, ": target must have B = ",
+              logits.size(0), " elements, got ", target.numel());
+}
+
+std::vector<at::Tensor> ce_masked_fwd(at::Tensor logits, at::Tensor target,
+                                      int64_t ignore_index) {
+  check_ce_masked("ce_masked_fwd", logits, target);
+  const int B = (int)logits.size(0), C = (int)logits.size(1);
+  auto lse = at::empty({B}, logits.options().dtype(at::kFloat));
+  auto loss = at::zeros({}, logits.options().dtype(at::kFloat));
+  auto n_valid = at::zeros({1}, logits.options().dtype(at::kInt));
+  launch_ce_masked_fwd(
+      is_bf16(logits), logits.data_ptr(),
+      reinterpret_cast<const long long*>(target.data_ptr<int64_t>()),
+      lse.data_ptr<float>(), loss.data_ptr<float>(), n_valid.data_ptr<int>(),
+      (long long)ignore_index, B, C, stream());
+  return {loss, lse, n_valid};
+}
+
+at::Tensor ce_masked_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
+                         at::Tensor n_valid, at::Tensor dout,
+                         int64_t ignore_index) {
+  const char* op = "ce_masked_bwd";
+  check_ce_masked(op, logits, target);
+  const int B = (int)logits.size(0), C = (int)logits.size(1);
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.dim() == 1 &&
+                  lse.size(0) == B && lse.is_contiguous(),
+              op, ": lse must be contiguous fp32 [B = ", B, "]");
+  TORCH_CHECK(lse.device() == logits.device(), op,
+              ": lse must be on the logits' device");
+  TORCH_CHECK(n_valid.scalar_type() == at::kInt && n_valid.numel() == 1, op,
+              ": n_valid must be int32 with 1 element");
+  TORCH_CHECK(n_valid.device() == logits.device(), op,
+              ": n_valid must be on the logits' device");
+  TORCH_CHECK(dout.scalar_type() == at::kFloat && dout.numel() == 1, op,
+              ": dout must be an fp32 scalar");
+  TORCH_CHECK(dout.device() == logits.device(), op,
+              ": dout must be on the logits' device");
+  auto dx = at::empty_like(logits);
+  launch_ce_masked_bwd(
+      is_bf16(logits), logits.data_ptr(),
+      reinterpret_cast<const long long*>(target.data_ptr<int64_t>()),
+      lse.data_ptr<float>(), n_valid.data_ptr<int>(), dout.data_ptr<float>(),
+      dx.data_ptr(), (long long)ignore_index, B, C, stream());
+  return dx;
+}
+
 // ---- layernorm / rmsnorm -----------------------------------------------------
 // One forward and one backward for both families and their fused forms:
 // center = LayerNorm (b, mean, db exist), res / plus = the fused residual add
@@ -1258,6 +1328,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mse_bwd", &mse_bwd);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);
+  m.def("ce_masked_fwd", &ce_masked_fwd);
+  m.def("ce_masked_bwd", &ce_masked_bwd);
   m.def("ln_fwd", &ln_fwd);
   m.def("ln_bwd", &ln_bwd);
   m.def("ln_add_fwd", &ln_add_fwd);

@@ -37,6 +37,17 @@ void launch_ce_fwd(bool is_bf16, const void* logits, const long long* target,
 void launch_ce_bwd(bool is_bf16, const void* logits, const long long* target,
                    const float* lse, const float* dout, void* dx, int B, int C,
                    hipStream_t s);
+// ignored labels: rows with target outside [0, C) or == ignore_index are
+// skipped; loss = mean over the live rows (0 when none), n_valid = their count,
+// both zeroed by the caller
+void launch_ce_masked_fwd(bool is_bf16, const void* logits,
+                          const long long* target, float* lse, float* loss,
+                          int* n_valid, long long ignore_index, int B, int C,
+                          hipStream_t s);
+void launch_ce_masked_bwd(bool is_bf16, const void* logits,
+                          const long long* target, const float* lse,
+                          const int* n_valid, const float* dout, void* dx,
+                          long long ignore_index, int B, int C, hipStream_t s);
 
 // norm.hip — LayerNorm (center) / RMSNorm rows and BatchNorm: each launches
 // exactly the grid, kernel form and LDS size the route names (norm_route.h

@@ -640,8 +640,102 @@ class CrossEntropyFn(torch.autograd.Function):
         return dx, None
 
 
-def cross_entropy(logits, target):
-    return CrossEntropyFn.apply(logits, target)
+def _ce_live(target, C: int, ignore_index: int):
+    """Live rows of the masked CE: a class index that is not ignore_index."""
+    return (target >= 0) & (target < C) & (target != ignore_index)
+
+
+class MaskedCrossEntropyFn(torch.autograd.Function):
+    """Fused CE with ignored labels: mean over the live rows (see
+    :func:`cross_entropy`). n_valid stays on the device between forward and
+    backward; nothing here reads a tensor back to the host."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index: int):
+        logits, target = logits.contiguous(), target.contiguous()
+        ctx.ignore_index = ignore_index
+        if _on_gpu(logits):
+            loss, lse, n_valid = require_hip().ce_masked_fwd(
+                logits, target, ignore_index)
+        else:
+            C = logits.shape[1]
+            live = _ce_live(target, C, ignore_index)
+            n_valid = live.sum().to(torch.int32).reshape(1)
+            lf = logits.float()
+            zero = torch.zeros((), dtype=torch.float32)
+            lse = torch.where(live, torch.logsumexp(lf, dim=1), zero)
+            t = torch.where(live, target, torch.zeros_like(target))
+            row = torch.where(live, lse - lf.gather(1, t[:, None]).squeeze(1),
+                              zero)
+            loss = row.sum() / n_valid[0].clamp(min=1)
+        ctx.save_for_backward(logits, target, lse, n_valid)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dout):
+        logits, target, lse, n_valid = ctx.saved_tensors
+        if _on_gpu(logits):
+            dx = require_hip().ce_masked_bwd(
+                logits, target, lse, n_valid, dout.float().contiguous(),
+                ctx.ignore_index)
+        else:
+            live = _ce_live(target, logits.shape[1], ctx.ignore_index)
+            t = torch.where(live, target, torch.zeros_like(target))
+            p = (logits.float() - lse[:, None]).exp()
+            p.scatter_add_(1, t[:, None],
+                           torch.full_like(t[:, None], -1.0,
+                                           dtype=torch.float32))
+            scale = dout.float() / n_valid[0].clamp(min=1)
+            dx = torch.where(live[:, None], p * scale,
+                             torch.zeros((), dtype=torch.float32))
+            dx = dx.to(logits.dtype)
+        return dx, None, None
+
+
+def cross_entropy(logits, target, ignore_index=None):
+    """Mean cross-entropy of [B, C] logits against int64 [B] class indices.
+
+    ``ignore_index=None`` is the dense loss: every row is scored, every label
+    must be a class, the mean is over B.
+
+    With an integer ``ignore_index`` a row is *live* iff ``0 <= target < C and
+    target != ignore_index``; every other row is ignored: its logits are never
+    read (they may hold anything), it gets a zero gradient row, and the mean
+    is over the live rows only. That covers ``ignore_index`` itself, in range
+    (a pad id) or not (-100), and also any other label outside [0, C): the
+    kernels never turn a label into an address without that test, so a wrong
+    label is skipped, not read out of bounds. Make it an error where the data
+    is prepared, with :func:`validate_labels`. The live-row count stays on the
+    device, so a captured graph can carry the call.
+
+    Deliberate difference from ``torch.nn.functional.cross_entropy``: a
+    minibatch with no live row gives loss 0 and a zero gradient, where torch
+    gives NaN (0 / 0). One empty client minibatch must not poison a federated
+    round."""
+    if ignore_index is None:
+        return CrossEntropyFn.apply(logits, target)
+    return MaskedCrossEntropyFn.apply(logits, target, int(ignore_index))
+
+
+def validate_labels(labels, num_classes: int, ignore_index=None):
+    """Host-side, data-preparation time: raise ValueError unless every label
+    is a class index in [0, num_classes) or equals ``ignore_index``, naming
+    the first offender. The masked CE kernels only *skip* such labels (and the
+    dense ones trust them), so this is where a wrong label becomes an error.
+    Returns ``labels``."""
+    if labels.dtype != torch.int64:
+        raise ValueError(f"labels must be int64, got {labels.dtype}")
+    bad = (labels < 0) | (labels >= num_classes)
+    if ignore_index is not None:
+        bad &= labels != ignore_index
+    if bool(bad.any()):
+        flat = bad.reshape(-1).nonzero()[0].item()
+        idx = tuple(int(i) for i in torch.unravel_index(
+            torch.tensor(flat), labels.shape)) if labels.dim() else ()
+        raise ValueError(
+            f"label {int(labels.reshape(-1)[flat])} at index {idx} is neither "
+            f"a class in [0, {num_classes}) nor ignore_index = {ignore_index}")
+    return labels
 
 
 class BatchedMatmulFn(torch.autograd.Function):

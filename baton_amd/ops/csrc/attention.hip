@@ -7,6 +7,9 @@
 // and causal masking — the score matrix is read once and written once.
 // Backward fuses the dsoftmax reduction: dx = scale * y * (dy - sum(dy*y)).
 #include "common.h"
+#include "attn_route.h"
+
+static_assert(kSoftmaxMaxGrid == kMaxGrid, "attn_route.h names this cap");
 
 // Per-sequence key lengths (right padding). The VARLEN instantiations take a
 // RowLens as their last argument: row r belongs to entry r / rows_per_len of
@@ -14,18 +17,16 @@
 // min(causal limit, L) with L = clamp(kv_len[entry], 0, C); a row whose query
 // position is >= L is stored as zeros without being read. The dense
 // instantiations take an empty struct and keep their code.
-struct NoLens {};
 struct RowLens {
   const int* kv_len;
   long long rows_per_len;
   int q_period;
 };
-template <bool VARLEN> struct LenArg { using type = NoLens; };
-template <> struct LenArg<true> { using type = RowLens; };
+template <bool VARLEN> using Lens = LenArg<VARLEN, RowLens>;
 
 // last visible column of row r given its dense limit qpos; -1: a dead row
 DEVINL int len_limit(const RowLens& lens, long long r, int C, int qpos) {
-  const int L = min(max(lens.kv_len[r / lens.rows_per_len], 0), C);
+  const int L = clamp_len(lens.kv_len[r / lens.rows_per_len], C);
   return (int)(r % lens.q_period) >= L ? -1 : min(qpos, L - 1);
 }
 
@@ -33,7 +34,7 @@ template <typename T, bool CAUSAL, bool VARLEN>
 __global__ void softmax_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
                                    long long R, int C, float scale,
                                    int causal_seq,
-                                   typename LenArg<VARLEN>::type lens) {
+                                   Lens<VARLEN> lens) {
   __shared__ float scratch[kBlock / kWave];
   __shared__ float s_max;
   for (long long r = blockIdx.x; r < R; r += gridDim.x) {
@@ -41,9 +42,7 @@ __global__ void softmax_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
     T* yrow = y + r * C;
     int qpos = CAUSAL ? (int)(r % causal_seq) : C - 1;
     constexpr int V = VecTraits<T>::kElems;
-    // vector path needs enough vectors to keep a wave busy: at C=128 it
-    // left 16 of 256 threads active and measured SLOWER than scalar
-    const bool vec = (C % V) == 0 && C >= V * 64;
+    const bool vec = softmax_vec(C, V);   // attn_route.h
     if constexpr (VARLEN) {
       qpos = len_limit(lens, r, C, qpos);
       if (qpos < 0) {   // block-uniform: the whole block skips the barriers
@@ -129,7 +128,7 @@ __global__ void softmax_bwd_kernel(const T* __restrict__ y,
     const T* dyrow = dy + r * C;
     T* dxrow = dx + r * C;
     constexpr int V = VecTraits<T>::kElems;
-    const bool vec = (C % V) == 0 && C >= V * 64;   // see fwd comment
+    const bool vec = softmax_vec(C, V);
     float acc = 0.f;
     if (vec) {
       for (int cv = threadIdx.x; cv < C / V; cv += blockDim.x) {
@@ -169,11 +168,11 @@ __global__ void softmax_bwd_kernel(const T* __restrict__ y,
 template <typename T, bool CAUSAL, bool VARLEN>
 __global__ __launch_bounds__(kBlock) void softmax_fwd_wave_kernel(
     const T* __restrict__ x, T* __restrict__ y, long long R, int C,
-    float scale, int causal_seq, typename LenArg<VARLEN>::type lens) {
+    float scale, int causal_seq, Lens<VARLEN> lens) {
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   constexpr int V = VecTraits<T>::kElems;
-  const bool vec = (C % V) == 0 && C >= V * 64;
+  const bool vec = softmax_vec(C, V);
   for (long long r = (long long)blockIdx.x * 4 + wid; r < R;
        r += (long long)gridDim.x * 4) {
     const T* row = x + r * C;
@@ -242,7 +241,7 @@ __global__ __launch_bounds__(kBlock) void softmax_bwd_wave_kernel(
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   constexpr int V = VecTraits<T>::kElems;
-  const bool vec = (C % V) == 0 && C >= V * 64;
+  const bool vec = softmax_vec(C, V);
   for (long long r = (long long)blockIdx.x * 4 + wid; r < R;
        r += (long long)gridDim.x * 4) {
     const T* yrow = y + r * C;
@@ -281,98 +280,40 @@ __global__ __launch_bounds__(kBlock) void softmax_bwd_wave_kernel(
   }
 }
 
-#define INST_SM_WAVE(T)                                                      \
-  template __global__ void softmax_fwd_wave_kernel<T, true, false>(          \
-      const T*, T*, long long, int, float, int, NoLens);                     \
-  template __global__ void softmax_fwd_wave_kernel<T, false, false>(         \
-      const T*, T*, long long, int, float, int, NoLens);                     \
-  template __global__ void softmax_fwd_wave_kernel<T, true, true>(           \
-      const T*, T*, long long, int, float, int, RowLens);                    \
-  template __global__ void softmax_fwd_wave_kernel<T, false, true>(          \
-      const T*, T*, long long, int, float, int, RowLens);                    \
-  template __global__ void softmax_bwd_wave_kernel<T>(const T*, const T*,    \
-                                                      T*, long long, int,    \
-                                                      float);
-
-INST_SM_WAVE(float)
-INST_SM_WAVE(bf16)
-
-#define INST_SM(T)                                                           \
-  template __global__ void softmax_fwd_kernel<T, true, false>(               \
-      const T*, T*, long long, int, float, int, NoLens);                     \
-  template __global__ void softmax_fwd_kernel<T, false, false>(              \
-      const T*, T*, long long, int, float, int, NoLens);                     \
-  template __global__ void softmax_fwd_kernel<T, true, true>(                \
-      const T*, T*, long long, int, float, int, RowLens);                    \
-  template __global__ void softmax_fwd_kernel<T, false, true>(               \
-      const T*, T*, long long, int, float, int, RowLens);                    \
-  template __global__ void softmax_bwd_kernel<T>(const T*, const T*, T*,     \
-                                                 long long, int, float);
-
-INST_SM(float)
-INST_SM(bf16)
-
 // ---- launchers -------------------------------------------------------------
 #include "launchers.h"
 
-// kv_len == nullptr launches the dense instantiations.
+// Kernel and grid come from softmax_route; kv_len == nullptr launches the
+// dense instantiations.
 void launch_softmax_fwd(bool is_bf16, const void* x, void* y, long long R,
                         int C, float scale, int causal_seq, const int* kv_len,
                         long long rows_per_len, int q_period, hipStream_t s) {
+  const SoftmaxRoute rt = softmax_route(R, C, is_bf16);
   const RowLens lens{kv_len, rows_per_len, q_period};
-  const bool causal = causal_seq > 0;
-#define SM_PICK(CALL, T)                                                     \
-  do {                                                                       \
-    if (kv_len) {                                                            \
-      if (causal) CALL(T, true, true, lens); else CALL(T, false, true, lens); \
-    } else {                                                                 \
-      if (causal) CALL(T, true, false, NoLens{});                            \
-      else CALL(T, false, false, NoLens{});                                  \
-    }                                                                        \
-  } while (0)
-  if (C <= 1024) {   // wave-per-row: 4 rows/block, no block barriers
-    const long long blocks = (R + 3) / 4;
-    const int grid = blocks < kMaxGrid ? (int)blocks : kMaxGrid;
-    #define SMW_CALL(T, CZ, VL, LENS)                                         \
-      hipLaunchKernelGGL((softmax_fwd_wave_kernel<T, CZ, VL>), dim3(grid),    \
-                         dim3(kBlock), 0, s, (const T*)x, (T*)y, R, C, scale, \
-                         causal_seq, LENS)
-    if (is_bf16) SM_PICK(SMW_CALL, bf16); else SM_PICK(SMW_CALL, float);
-    #undef SMW_CALL
-    return;
-  }
-  const int grid = R < kMaxGrid ? (int)R : kMaxGrid;
-  #define SM_CALL(T, CZ, VL, LENS)                                           \
-    hipLaunchKernelGGL((softmax_fwd_kernel<T, CZ, VL>), dim3(grid),          \
-                       dim3(kBlock), 0, s, (const T*)x, (T*)y, R, C, scale,  \
-                       causal_seq, LENS)
-  if (is_bf16) SM_PICK(SM_CALL, bf16); else SM_PICK(SM_CALL, float);
-  #undef SM_CALL
-#undef SM_PICK
+  auto launch = [&](auto t, auto cz, auto vl) {
+    using T = decltype(t);
+    constexpr bool CZ = decltype(cz)::value, VL = decltype(vl)::value;
+    Lens<VL> la;
+    if constexpr (VL) la = lens;
+    hipLaunchKernelGGL((rt.wave ? softmax_fwd_wave_kernel<T, CZ, VL>
+                                : softmax_fwd_kernel<T, CZ, VL>),
+                       dim3(rt.grid), dim3(kBlock), 0, s, (const T*)x, (T*)y,
+                       R, C, scale, causal_seq, la);
+  };
+  dispatch2(causal_seq > 0, kv_len != nullptr, [&](auto cz, auto vl) {
+    if (is_bf16) launch(bf16{}, cz, vl); else launch(float{}, cz, vl);
+  });
 }
 
 void launch_softmax_bwd(bool is_bf16, const void* y, const void* dy, void* dx,
                         long long R, int C, float scale, hipStream_t s) {
-  if (C <= 1024) {
-    const long long blocks = (R + 3) / 4;
-    const int grid = blocks < kMaxGrid ? (int)blocks : kMaxGrid;
-    if (is_bf16)
-      hipLaunchKernelGGL(softmax_bwd_wave_kernel<bf16>, dim3(grid),
-                         dim3(kBlock), 0, s, (const bf16*)y, (const bf16*)dy,
-                         (bf16*)dx, R, C, scale);
-    else
-      hipLaunchKernelGGL(softmax_bwd_wave_kernel<float>, dim3(grid),
-                         dim3(kBlock), 0, s, (const float*)y, (const float*)dy,
-                         (float*)dx, R, C, scale);
-    return;
-  }
-  const int grid = R < kMaxGrid ? (int)R : kMaxGrid;
-  if (is_bf16)
-    hipLaunchKernelGGL(softmax_bwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0,
-                       s, (const bf16*)y, (const bf16*)dy, (bf16*)dx, R, C,
-                       scale);
-  else
-    hipLaunchKernelGGL(softmax_bwd_kernel<float>, dim3(grid), dim3(kBlock), 0,
-                       s, (const float*)y, (const float*)dy, (float*)dx, R, C,
-                       scale);
+  const SoftmaxRoute rt = softmax_route(R, C, is_bf16);
+  auto launch = [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(
+        (rt.wave ? softmax_bwd_wave_kernel<T> : softmax_bwd_kernel<T>),
+        dim3(rt.grid), dim3(kBlock), 0, s, (const T*)y, (const T*)dy, (T*)dx,
+        R, C, scale);
+  };
+  if (is_bf16) launch(bf16{}); else launch(float{});
 }

@@ -1170,29 +1170,40 @@ std::vector<at::Tensor> silu_mul_bwd(at::Tensor dy, at::Tensor a, at::Tensor b) 
 // ---- flash attention -------------------------------------------------------
 
 namespace {
-// q/k/v/o are 4-D [B,S,heads,DH] strided VIEWS with contiguous DH. The
-// kernels move 16-byte vectors at element offsets that are multiples of 8
-// from (batch, seq, head) row starts, so the base pointer and the three outer
-// strides must keep every such access 16-byte aligned.
-void check_attn_view(const at::Tensor& t, const char* name,
-                     const at::Tensor& q) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, name,
-              " must be a bf16 GPU tensor");
-  TORCH_CHECK(t.device() == q.device(), name, " must be on q's device");
-  TORCH_CHECK(t.dim() == 4, name, " must be [B,S,h,dh]");
-  TORCH_CHECK(t.stride(3) == 1, name, " head_dim must be contiguous");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
-              " must start on a 16-byte boundary");
-  TORCH_CHECK(t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
-                  t.stride(2) % 8 == 0,
-              name, " strides must be multiples of 8 elements (16 bytes)");
+// The problem of 4-D views in kFlashViewName order: q, k, v[, o[, dout, dq,
+// dk, dv]]. Sizes are q's, the kv head count is k's.
+FlashProblem flash_problem(std::initializer_list<const at::Tensor*> views,
+                           bool causal, bool varlen) {
+  const at::Tensor& q = **views.begin();
+  FlashProblem p{};
+  p.B = q.size(0), p.S = q.size(1), p.H = q.size(2), p.DH = q.size(3);
+  p.KVH = (*(views.begin() + 1))->size(2);
+  p.causal = causal, p.varlen = varlen;
+  for (const at::Tensor* t : views)
+    p.view[p.nviews++] = AttnView{
+        t->scalar_type() == at::kBFloat16, t->stride(0), t->stride(1),
+        t->stride(2), t->stride(3),
+        (int)(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16)};
+  return p;
 }
-void check_head_dim(int64_t DH) {
-  TORCH_CHECK(DH == 32 || DH == 64 || DH == 128,
-              "flash: unsupported head_dim ", DH);
+// What needs the tensors themselves, on every view; then the problem and its
+// route, whose refusal (layout, head dim, head counts) is the error.
+std::pair<FlashProblem, FlashRoute> checked_flash_problem(
+    std::initializer_list<const at::Tensor*> views, bool causal, bool varlen) {
+  int i = 0;
+  for (const at::Tensor* t : views) {
+    const char* name = kFlashViewName[i++];
+    TORCH_CHECK(t->is_cuda(), name, " must be a bf16 GPU tensor");
+    TORCH_CHECK(t->device() == (*views.begin())->device(), name,
+                " must be on q's device");
+    TORCH_CHECK(t->dim() == 4, name, " must be [B,S,h,dh]");
+  }
+  const FlashProblem p = flash_problem(views, causal, varlen);
+  const FlashRoute rt = flash_route(p);
+  TORCH_CHECK(rt.eligible, rt.refusal);
+  return {p, rt};
 }
 // k and v against q: same batch, sequence and head_dim, one kv head count
-// that divides q's.
 void check_kv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
   for (int d : {0, 1, 3}) {
     TORCH_CHECK(k.size(d) == q.size(d), "k must share q's B, S and dh: k is ",
@@ -1201,44 +1212,35 @@ void check_kv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
                 v.sizes(), ", q is ", q.sizes());
   }
   TORCH_CHECK(k.size(2) == v.size(2), "k and v must have the same head count");
-  TORCH_CHECK(k.size(2) > 0 && q.size(2) % k.size(2) == 0,
-              "q heads must be a multiple of kv heads");
 }
 void check_like_q(const at::Tensor& t, const char* name, const at::Tensor& q) {
   TORCH_CHECK(t.sizes() == q.sizes(), name, " must have q's sizes ", q.sizes(),
               ", got ", t.sizes());
 }
-void strides3(const at::Tensor& t, long long* out) {
-  out[0] = t.stride(0);  // batch
-  out[1] = t.stride(1);  // seq
-  out[2] = t.stride(2);  // head
-}
 }  // namespace
+
+// Whether the fused kernels take these q, k, v views: flash_route's answer.
+bool flash_eligible(const at::Tensor& q, const at::Tensor& k,
+                    const at::Tensor& v) {
+  for (const at::Tensor* t : {&q, &k, &v})
+    if (!t->is_cuda() || t->dim() != 4) return false;
+  return flash_route(flash_problem({&q, &k, &v}, false, false)).eligible;
+}
 
 std::vector<at::Tensor> flash_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                   at::Tensor o, bool causal,
                                   c10::optional<at::Tensor> seq_lens) {
-  check_attn_view(q, "q", q);
-  check_attn_view(k, "k", q);
-  check_attn_view(v, "v", q);
-  check_attn_view(o, "o", q);
-  check_head_dim(q.size(3));
+  const auto [p, rt] =
+      checked_flash_problem({&q, &k, &v, &o}, causal, seq_lens.has_value());
   check_kv(q, k, v);
   check_like_q(o, "o", q);
-  const int B = q.size(0), S = q.size(1), H = q.size(2), DH = q.size(3);
-  const int KVH = k.size(2);
-  const int G = H / KVH;
-  const int* lens = check_lens(seq_lens, "seq_lens", q, B, "B");
-  auto lse = at::empty({(long long)B * H, S},
+  FlashArgs a{};
+  a.seq_lens = check_lens(seq_lens, "seq_lens", q, p.B, "B");
+  auto lse = at::empty({(long long)p.B * p.H, p.S},
                        q.options().dtype(at::kFloat));
-  long long qs[3], ks[3], vs[3], os[3];
-  strides3(q, qs); strides3(k, ks); strides3(v, vs); strides3(o, os);
-  const float scale = 1.0f / std::sqrt((float)DH);
-  TORCH_CHECK(
-      launch_flash_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                       lse.data_ptr<float>(), B, S, H, G, DH, scale, causal,
-                       qs, ks, vs, os, lens, stream()),
-      "flash_fwd: unsupported head_dim ", DH);
+  a.q = q.data_ptr(), a.k = k.data_ptr(), a.v = v.data_ptr();
+  a.o = o.data_ptr(), a.lse = lse.data_ptr<float>();
+  launch_flash_fwd(rt, p, a, 1.0f / std::sqrt((float)p.DH), stream());
   return {o, lse};
 }
 
@@ -1246,15 +1248,8 @@ void flash_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                at::Tensor dout, at::Tensor lse, at::Tensor dq, at::Tensor dk,
                at::Tensor dv, bool causal,
                c10::optional<at::Tensor> seq_lens) {
-  check_attn_view(q, "q", q);
-  check_attn_view(k, "k", q);
-  check_attn_view(v, "v", q);
-  check_attn_view(o, "o", q);
-  check_attn_view(dout, "dout", q);
-  check_attn_view(dq, "dq", q);
-  check_attn_view(dk, "dk", q);
-  check_attn_view(dv, "dv", q);
-  check_head_dim(q.size(3));
+  const auto [p, rt] = checked_flash_problem(
+      {&q, &k, &v, &o, &dout, &dq, &dk, &dv}, causal, seq_lens.has_value());
   check_kv(q, k, v);
   check_like_q(o, "o", q);
   check_like_q(dout, "dout", q);
@@ -1262,38 +1257,67 @@ void flash_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
   // dk/dv are per-q-head [B,S,H,dh] (GQA callers group-sum)
   check_like_q(dk, "dk (per q head)", q);
   check_like_q(dv, "dv (per q head)", q);
-  const int B = q.size(0), S = q.size(1), H = q.size(2), DH = q.size(3);
-  const int KVH = k.size(2);
-  const int G = H / KVH;
   TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() &&
                   lse.scalar_type() == at::kFloat && lse.is_contiguous(),
               "lse must be a contiguous fp32 tensor on q's device");
-  TORCH_CHECK(lse.dim() == 2 && lse.size(0) == (int64_t)B * H &&
-                  lse.size(1) == S,
-              "lse must be [B*H, S] = [", (int64_t)B * H, ", ", S, "], got ",
-              lse.sizes());
-  const int* lens = check_lens(seq_lens, "seq_lens", q, B, "B");
+  TORCH_CHECK(lse.dim() == 2 && lse.size(0) == (int64_t)p.B * p.H &&
+                  lse.size(1) == p.S,
+              "lse must be [B*H, S] = [", (int64_t)p.B * p.H, ", ", p.S,
+              "], got ", lse.sizes());
+  FlashArgs a{};
+  a.seq_lens = check_lens(seq_lens, "seq_lens", q, p.B, "B");
   auto delta = at::empty_like(lse);
-  long long qs[3], ks[3], vs[3], os[3], dos[3], dqs[3], dks[3], dvs[3];
-  strides3(q, qs); strides3(k, ks); strides3(v, vs); strides3(o, os);
-  strides3(dout, dos); strides3(dq, dqs); strides3(dk, dks); strides3(dv, dvs);
-  const float scale = 1.0f / std::sqrt((float)DH);
-  launch_flash_delta(dout.data_ptr(), o.data_ptr(), delta.data_ptr<float>(),
-                     B, S, H, DH, dos, os, lens, stream());
-  TORCH_CHECK(
-      launch_flash_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                          dout.data_ptr(), lse.data_ptr<float>(),
-                          delta.data_ptr<float>(), dq.data_ptr(), B, S, H, G,
-                          DH, scale, causal, qs, ks, vs, dos, dqs, lens,
-                          stream()),
-      "flash_bwd_dq: unsupported head_dim ", DH);
-  TORCH_CHECK(
-      launch_flash_bwd_dkv(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                           dout.data_ptr(), lse.data_ptr<float>(),
-                           delta.data_ptr<float>(), dk.data_ptr(),
-                           dv.data_ptr(), B, S, H, G, DH, scale, causal, qs,
-                           ks, vs, dos, dks, dvs, lens, stream()),
-      "flash_bwd_dkv: unsupported head_dim ", DH);
+  a.q = q.data_ptr(), a.k = k.data_ptr(), a.v = v.data_ptr();
+  a.o = o.data_ptr(), a.lse = lse.data_ptr<float>();
+  a.dout = dout.data_ptr(), a.delta = delta.data_ptr<float>();
+  a.dq = dq.data_ptr(), a.dk = dk.data_ptr(), a.dv = dv.data_ptr();
+  const float scale = 1.0f / std::sqrt((float)p.DH);
+  launch_flash_delta(rt, p, a, stream());
+  launch_flash_bwd_dq(rt, p, a, scale, stream());
+  launch_flash_bwd_dkv(rt, p, a, scale, stream());
+}
+
+// What attn_route.h decides, from plain numbers (no GPU needed). views maps a
+// view name to (4 strides, base address % 16); the views not named are
+// contiguous [B, S, heads, DH]. bwd adds dout, dq, dk, dv to q, k, v, o.
+py::dict flash_route_py(int64_t B, int64_t S, int64_t H, int64_t KVH,
+                        int64_t DH, bool bf16, bool causal, bool varlen,
+                        bool bwd, const py::dict& views) {
+  using namespace py::literals;
+  TORCH_CHECK(B > 0 && S > 0 && H > 0 && DH > 0 && KVH >= 0 &&
+                  B * H <= INT_MAX && S <= INT_MAX && DH <= INT_MAX,
+              "flash_route: bad shape");
+  FlashProblem p{};
+  p.B = B, p.S = S, p.H = H, p.KVH = KVH, p.DH = DH;
+  p.causal = causal, p.varlen = varlen;
+  p.nviews = bwd ? (int)kFlashMaxViews : 4;
+  for (int i = 0; i < p.nviews; ++i) {
+    const int64_t heads = (i == kK || i == kV) ? KVH : H;
+    p.view[i] = AttnView{bf16, S * heads * DH, heads * DH, DH, 1, 0};
+    if (views.contains(kFlashViewName[i])) {
+      const auto t = views[kFlashViewName[i]].cast<std::array<int64_t, 5>>();
+      p.view[i] = AttnView{bf16, t[0], t[1], t[2], t[3], (int)t[4]};
+    }
+  }
+  const FlashRoute rt = flash_route(p);
+  auto grid = [](const int* g) { return py::make_tuple(g[0], g[1]); };
+  return py::dict(
+      "eligible"_a = rt.eligible,
+      "refusal"_a = rt.eligible ? py::object(py::none())
+                                : py::object(py::str(rt.refusal)),
+      "G"_a = rt.G, "grid_fwd"_a = grid(rt.grid_fwd),
+      "grid_delta"_a = grid(rt.grid_delta), "grid_dq"_a = grid(rt.grid_dq),
+      "grid_dkv"_a = grid(rt.grid_dkv), "lds_fwd"_a = rt.lds_fwd,
+      "lds_dq"_a = rt.lds_dq, "lds_dkv"_a = rt.lds_dkv);
+}
+
+py::dict softmax_route_py(int64_t rows, int64_t C, bool bf16) {
+  using namespace py::literals;
+  TORCH_CHECK(rows > 0 && C > 0 && C <= INT_MAX, "softmax_route: bad shape");
+  const SoftmaxRoute rt = softmax_route(rows, (int)C, bf16);
+  return py::dict("kernel"_a = rt.wave ? "wave" : "block", "vec"_a = rt.vec,
+                  "rows_per_block"_a = rt.rows_per_block, "grid"_a = rt.grid,
+                  "capped"_a = rt.capped);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1303,6 +1327,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("dq"),
         py::arg("dk"), py::arg("dv"), py::arg("causal"),
         py::arg("seq_lens") = py::none());
+  m.def("flash_eligible", &flash_eligible);
+  m.def("flash_route", &flash_route_py, py::arg("B"), py::arg("S"),
+        py::arg("H"), py::arg("KVH"), py::arg("DH"), py::arg("bf16") = true,
+        py::arg("causal") = false, py::arg("varlen") = false,
+        py::arg("bwd") = false, py::arg("views") = py::dict());
+  m.def("softmax_route", &softmax_route_py, py::arg("rows"), py::arg("C"),
+        py::arg("bf16"));
   m.def("rms_add_fwd", &rms_add_fwd);
   m.def("rms_bwd_plus", &rms_bwd_plus);
   m.def("sgd_step", &sgd_step, "fused SGD step", py::arg("p"), py::arg("g"),

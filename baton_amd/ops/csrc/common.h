@@ -124,6 +124,24 @@ DEVINL void row_walk(int C, F&& body) {
   }
 }
 
+// ---- per-sequence lengths (attention) ------------------------------------
+// Last argument of a kernel with a VARLEN flag: its lengths (type L), or an
+// empty struct so that the dense instantiations keep their code.
+struct NoLens {};
+template <bool VARLEN, typename L>
+using LenArg = std::conditional_t<VARLEN, L, NoLens>;
+// clamped into [0, S]: a bad length cannot move an access out of bounds
+DEVINL int clamp_len(int len, int S) { return min(max(len, 0), S); }
+
+// Host dispatch over two template flags: f(bool_constant<a>, bool_constant<b>)
+template <typename F>
+void dispatch2(bool a, bool b, F&& f) {
+  auto on_a = [&](auto A) {
+    if (b) f(A, std::true_type{}); else f(A, std::false_type{});
+  };
+  if (a) on_a(std::true_type{}); else on_a(std::false_type{});
+}
+
 // ---- reductions ----------------------------------------------------------
 
 DEVINL float wave_reduce_sum(float v) {

@@ -5,8 +5,8 @@
 // kernel walks K/V tiles with an online softmax, so scores never touch HBM
 // and the softmax/transpose/dP round-trips disappear from the profile
 // (reference computation: torch softmax(QK^T)V inside
-// nn.MultiheadAttention-equivalents — /root/reference has no attention at
-// all, this serves the BERT/Llama BASELINE configs).
+// nn.MultiheadAttention-equivalents; this serves the BERT/Llama BASELINE
+// configs).
 //
 // Structure (CDNA4 guide §B "fused attention prefill" recipe, adapted):
 //   * workgroup = 4 waves x 32 q rows = 128 q rows of one (batch, q-head);
@@ -37,26 +37,39 @@
 //   * dK/dV kernel (kv-tile-major, each wave owns 32 kv rows): S/P/dP in
 //     the mirrored orientation (kv lane-local), dV^T += mfma(A=dO^T, B=P),
 //     dK^T += mfma(A=Q^T, B=dS) with Q/dO staged row-major AND transposed.
+// Tile sizes, grids and LDS sizes are attn_route.h's.
+#include <stdexcept>
+
 #include "common.h"
+#include "launchers.h"
 
 namespace fa {
 
-constexpr int THREADS = 256;       // 4 waves
-constexpr int QW = 32;             // q rows per wave
-constexpr int QB = 128;            // q rows per block
-constexpr int KVB = 64;            // kv tile
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-DEVINL float bf2f(short h) {
-  return __uint_as_float(((unsigned int)(unsigned short)h) << 16);
-}
 
 // pack two f32 into one dword of 2 bf16 (compiler emits v_cvt_pk_bf16_f32)
 DEVINL unsigned int pk_bf16(float lo, float hi) {
   __hip_bfloat162 t = __float22bfloat162_rn(float2{lo, hi});
   return *reinterpret_cast<unsigned int*>(&t);
+}
+
+// eight consecutive fp32 -> one bf16 MFMA fragment (T12 half-swap)
+DEVINL s16x8 pack_frag(const float* p) {
+  unsigned int A = pk_bf16(p[0], p[1]);
+  unsigned int B = pk_bf16(p[2], p[3]);
+  unsigned int C = pk_bf16(p[4], p[5]);
+  unsigned int D = pk_bf16(p[6], p[7]);
+  {
+    u32x2 r = __builtin_amdgcn_permlane32_swap(A, C, false, false);
+    A = r[0]; C = r[1];
+  }
+  {
+    u32x2 r = __builtin_amdgcn_permlane32_swap(B, D, false, false);
+    B = r[0]; D = r[1];
+  }
+  unsigned int dw[4] = {A, B, C, D};
+  return *reinterpret_cast<const s16x8*>(dw);
 }
 
 // K image: [KVB][DH] with 16-B slot XOR (row stride is power of two; the
@@ -70,10 +83,38 @@ DEVINL int koff(int kv, int d) {
 DEVINL int voff(int d, int kv) {
   return d * KVB + ((((kv >> 3) ^ d) & 7) << 3) + (kv & 7);
 }
+// Q^T / dO^T images of dk/dv: [DH][32] (rows are d, cols are q)
+DEVINL int qtoff(int d, int q) {
+  return d * 32 + ((((q >> 3) ^ d) & 3) << 3) + (q & 7);
+}
 
 DEVINL s16x8 lds128(const bf16* p) {
   return *reinterpret_cast<const __attribute__((address_space(3)))
              s16x8*>((const __attribute__((address_space(3))) bf16*)p);
+}
+DEVINL void lds_store128(bf16* p, s16x8 v) {
+  *reinterpret_cast<__attribute__((address_space(3))) s16x8*>(
+      (__attribute__((address_space(3))) bf16*)p) = v;
+}
+
+// 16-byte chunk idx of a [rows][DH] tile: its tile row and 8-element slot
+template <int DH> DEVINL int chunk_row(int idx) { return idx / (DH / 8); }
+template <int DH> DEVINL int chunk_slot(int idx) { return idx % (DH / 8); }
+
+// that chunk of two operands (row strides lda, ldb) whose tile starts at
+// global row r0; zero from global row L on
+template <int DH>
+DEVINL void load_chunk2(int idx, int r0, int L, const bf16* A, long long lda,
+                        const bf16* B, long long ldb, s16x8& a, s16x8& b) {
+  const int g = r0 + chunk_row<DH>(idx);
+  const int slot = chunk_slot<DH>(idx);
+  if (g < L) {
+    a = *reinterpret_cast<const s16x8*>(&A[(long long)g * lda + slot * 8]);
+    b = *reinterpret_cast<const s16x8*>(&B[(long long)g * ldb + slot * 8]);
+  } else {
+    a = s16x8{};
+    b = s16x8{};
+  }
 }
 
 // ---- per-sequence lengths ---------------------------------------------------
@@ -85,26 +126,47 @@ DEVINL s16x8 lds128(const bf16* p) {
 // the dense kernel on the [:L_b] slices and are bit-identical to it. Rows
 // L_b .. S-1 of every output are stored as +0; nothing is read from them.
 // The dense instantiations take an empty struct instead and keep their code.
-struct NoLens {};
-template <bool VARLEN> struct LenArg { using type = NoLens; };
-template <> struct LenArg<true> { using type = const int*; };
+template <bool VARLEN> using Lens = LenArg<VARLEN, const int*>;
 
 // block-uniform (b comes from blockIdx): stays in an SGPR. Clamped into
 // [0, S] so a bad length cannot move an access out of bounds.
 template <bool VARLEN>
-DEVINL int live_len(typename LenArg<VARLEN>::type lens, int b, int S) {
-  if constexpr (VARLEN) return min(max(lens[b], 0), S);
+DEVINL int live_len(Lens<VARLEN> lens, int b, int S) {
+  if constexpr (VARLEN) return clamp_len(lens[b], S);
   else return S;
 }
 
-// one lane's share of a [.., DH] output row (the epilogues' store pattern)
+// one lane's share of a [.., DH] output row (the epilogues' store pattern):
+// 4-element run qd of 32-column block db starts at this element
+DEVINL int run_off(int db, int qd, int hi) { return db * 32 + qd * 8 + hi * 4; }
+
 template <int DH>
 DEVINL void store_zero_row(bf16* row, int hi) {
 #pragma unroll
   for (int db = 0; db < DH / 32; ++db)
 #pragma unroll
     for (int qd = 0; qd < 4; ++qd)
-      *reinterpret_cast<u32x2*>(&row[db * 32 + qd * 8 + hi * 4]) = u32x2{0u, 0u};
+      *reinterpret_cast<u32x2*>(&row[run_off(db, qd, hi)]) = u32x2{0u, 0u};
+}
+
+// the accumulators' row, stored as bf16; SCALED (compile time, so the others
+// keep their code) multiplies by mul first: the forward's 1 / l
+template <int DH, bool SCALED = false>
+DEVINL void store_row(bf16* row, const f32x16* acc, int hi, float mul = 1.f) {
+#pragma unroll
+  for (int db = 0; db < DH / 32; ++db)
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+      unsigned int w0, w1;
+      if constexpr (SCALED) {
+        w0 = pk_bf16(acc[db][qd * 4 + 0] * mul, acc[db][qd * 4 + 1] * mul);
+        w1 = pk_bf16(acc[db][qd * 4 + 2] * mul, acc[db][qd * 4 + 3] * mul);
+      } else {
+        w0 = pk_bf16(acc[db][qd * 4 + 0], acc[db][qd * 4 + 1]);
+        w1 = pk_bf16(acc[db][qd * 4 + 2], acc[db][qd * 4 + 3]);
+      }
+      *reinterpret_cast<u32x2*>(&row[run_off(db, qd, hi)]) = u32x2{w0, w1};
+    }
 }
 
 // ---- forward ---------------------------------------------------------------
@@ -120,12 +182,12 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
     long long skB, long long skS, long long skH,
     long long svB, long long svS, long long svH,
     long long soB, long long soS, long long soH,
-    typename LenArg<VARLEN>::type lens) {
+    Lens<VARLEN> lens) {
   constexpr int F = DH / 16;        // QK^T mfma count per 32-kv subtile
   constexpr int DB = DH / 32;       // O^T 32-row blocks
   constexpr int NCK = DH / 32;      // 16-B staging chunks per thread/operand
 
-  __shared__ bf16 lds[2 * KVB * DH + 2 * DH * KVB];
+  __shared__ bf16 lds[fwd_lds_bytes(DH) / sizeof(bf16)];
   auto kbuf = [&](int b) -> bf16* { return lds + b * KVB * DH; };
   auto vbuf = [&](int b) -> bf16* { return lds + 2 * KVB * DH + b * DH * KVB; };
 
@@ -181,35 +243,19 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
   // ---- staging helpers (register-staged; T14 split) ----
   s16x8 kreg[NCK], vreg[NCK];
   auto stage_load = [&](int t) {
-    const int k0 = t * KVB;
 #pragma unroll
-    for (int c = 0; c < NCK; ++c) {
-      const int idx = c * THREADS + tid;
-      const int kv = idx / (DH / 8);
-      const int slot = idx % (DH / 8);
-      const int kvg = k0 + kv;
-      if (kvg < L) {
-        kreg[c] = *reinterpret_cast<const s16x8*>(
-            &Kp[(long long)kvg * skS + slot * 8]);
-        vreg[c] = *reinterpret_cast<const s16x8*>(
-            &Vp[(long long)kvg * svS + slot * 8]);
-      } else {
-        kreg[c] = s16x8{};
-        vreg[c] = s16x8{};
-      }
-    }
+    for (int c = 0; c < NCK; ++c)
+      load_chunk2<DH>(c * THREADS + tid, t * KVB, L, Kp, skS, Vp, svS,
+                      kreg[c], vreg[c]);
   };
   auto stage_write = [&](int buf) {
     bf16* kb = kbuf(buf);
     bf16* vb = vbuf(buf);
 #pragma unroll
     for (int c = 0; c < NCK; ++c) {
-      const int idx = c * THREADS + tid;
-      const int kv = idx / (DH / 8);
-      const int slot = idx % (DH / 8);
-      *reinterpret_cast<__attribute__((address_space(3))) s16x8*>(
-          (__attribute__((address_space(3))) bf16*)&kb[koff<DH>(kv, slot * 8)]) =
-          kreg[c];
+      const int kv = chunk_row<DH>(c * THREADS + tid);
+      const int slot = chunk_slot<DH>(c * THREADS + tid);
+      lds_store128(&kb[koff<DH>(kv, slot * 8)], kreg[c]);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         vb[voff(slot * 8 + j, kv)] = ((const bf16*)&vreg[c])[j];
@@ -267,29 +313,13 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) o_acc[db][r] *= alpha;
 
-      // P -> bf16 fragments (T12 half-swap); frag[st][halfk]
+      // P -> bf16 fragments; frag[st][halfk]
       s16x8 pf[2][2];
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
         const float* p = st == 0 ? p0 : p1;
 #pragma unroll
-        for (int hk = 0; hk < 2; ++hk) {
-          const int o8 = hk * 8;
-          unsigned int A = pk_bf16(p[o8 + 0], p[o8 + 1]);
-          unsigned int B = pk_bf16(p[o8 + 2], p[o8 + 3]);
-          unsigned int C = pk_bf16(p[o8 + 4], p[o8 + 5]);
-          unsigned int D = pk_bf16(p[o8 + 6], p[o8 + 7]);
-          {
-            u32x2 r = __builtin_amdgcn_permlane32_swap(A, C, false, false);
-            A = r[0]; C = r[1];
-          }
-          {
-            u32x2 r = __builtin_amdgcn_permlane32_swap(B, D, false, false);
-            B = r[0]; D = r[1];
-          }
-          unsigned int dw[4] = {A, B, C, D};
-          pf[st][hk] = *reinterpret_cast<const s16x8*>(dw);
-        }
+        for (int hk = 0; hk < 2; ++hk) pf[st][hk] = pack_frag(p + hk * 8);
       }
       // PV: O^T += V^T-frag x P-frag
       const bf16* vbp = vbuf(cur);
@@ -322,18 +352,7 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
   }
   const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
   if (lane < 32) LSE[(long long)bh * S + qg] = m_run + __logf(fmaxf(l_run, 1e-30f));
-  bf16* orow = Op + (long long)qg * soS;
-#pragma unroll
-  for (int db = 0; db < DB; ++db)
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const int d0 = db * 32 + qd * 8 + hi * 4;
-      const unsigned int w0 =
-          pk_bf16(o_acc[db][qd * 4 + 0] * inv, o_acc[db][qd * 4 + 1] * inv);
-      const unsigned int w1 =
-          pk_bf16(o_acc[db][qd * 4 + 2] * inv, o_acc[db][qd * 4 + 3] * inv);
-      *reinterpret_cast<u32x2*>(&orow[d0]) = u32x2{w0, w1};
-    }
+  store_row<DH, true>(Op + (long long)qg * soS, o_acc, hi, inv);
 }
 
 // ---- backward --------------------------------------------------------------
@@ -342,22 +361,22 @@ __global__ __launch_bounds__(THREADS) void flash_fwd_kernel(
 // grid: (ceil(S/4), B*H); one wave per (bh, q) row. DH is a multiple of 8,
 // so lanes 0..DH/8-1 each reduce one 16-B chunk.
 template <int DH, bool VARLEN>
-__global__ __launch_bounds__(256) void flash_delta_kernel(
+__global__ __launch_bounds__(THREADS) void flash_delta_kernel(
     const bf16* __restrict__ dO, const bf16* __restrict__ O,
     float* __restrict__ DELTA, int S, int H,
-    long long doB, long long doS, long long doH,
-    long long oB, long long oS, long long oH,
-    typename LenArg<VARLEN>::type lens) {
+    long long sdoB, long long sdoS, long long sdoH,
+    long long soB, long long soS, long long soH,
+    Lens<VARLEN> lens) {
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
-  const int q = blockIdx.x * 4 + wid;
+  const int q = blockIdx.x * DELTA_ROWS + wid;
   if (q >= S) return;
   const int bh = blockIdx.y;
   const int b = bh / H, h = bh % H;
   // padded rows are not read; dq and dk/dv never consume their delta
   if (VARLEN && q >= live_len<VARLEN>(lens, b, S)) return;
-  const bf16* dop = dO + b * doB + h * doH + (long long)q * doS;
-  const bf16* op = O + b * oB + h * oH + (long long)q * oS;
+  const bf16* dop = dO + b * sdoB + h * sdoH + (long long)q * sdoS;
+  const bf16* op = O + b * soB + h * soH + (long long)q * soS;
   float acc = 0.f;
   if (lane * 8 < DH) {
     float fd[8], fo[8];
@@ -383,15 +402,15 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
     long long sqB, long long sqS, long long sqH,
     long long skB, long long skS, long long skH,
     long long svB, long long svS, long long svH,
-    long long doB, long long doS, long long doH,
-    long long dqB, long long dqS, long long dqH,
-    typename LenArg<VARLEN>::type lens) {
+    long long sdoB, long long sdoS, long long sdoH,
+    long long sdqB, long long sdqS, long long sdqH,
+    Lens<VARLEN> lens) {
   constexpr int F = DH / 16;
   constexpr int DB = DH / 32;
   constexpr int NCK = DH / 32;
 
   // K rows | V rows | K^T — single-buffered (2-phase per tile)
-  __shared__ bf16 lds[3 * KVB * DH];
+  __shared__ bf16 lds[dq_lds_bytes(DH) / sizeof(bf16)];
   bf16* kb = lds;
   bf16* vb = lds + KVB * DH;
   bf16* ktb = lds + 2 * KVB * DH;
@@ -408,14 +427,14 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
   const bf16* Qp = Q + b * sqB + h * sqH;
   const bf16* Kp = K + b * skB + kvh * skH;
   const bf16* Vp = V + b * svB + kvh * svH;
-  const bf16* dOp = dO + b * doB + h * doH;
-  bf16* dQp = dQ + b * dqB + h * dqH;
+  const bf16* dOp = dO + b * sdoB + h * sdoH;
+  bf16* dQp = dQ + b * sdqB + h * sdqH;
 
   const int q0 = blockIdx.x * QB;
   const int qg = q0 + wid * QW + lq;
   const int L = live_len<VARLEN>(lens, b, S);
   if (VARLEN && q0 >= L) {        // dead block: whole block, before any barrier
-    if (qg < S) store_zero_row<DH>(dQp + (long long)qg * dqS, hi);
+    if (qg < S) store_zero_row<DH>(dQp + (long long)qg * sdqS, hi);
     return;
   }
   const bool qvalid = qg < L;
@@ -428,7 +447,7 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
       qf[f] = *reinterpret_cast<const s16x8*>(
           &Qp[(long long)qg * sqS + f * 16 + hi * 8]);
       dof[f] = *reinterpret_cast<const s16x8*>(
-          &dOp[(long long)qg * doS + f * 16 + hi * 8]);
+          &dOp[(long long)qg * sdoS + f * 16 + hi * 8]);
     } else {
       qf[f] = s16x8{};
       dof[f] = s16x8{};
@@ -448,21 +467,12 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < NCK; ++c) {
-      const int idx = c * THREADS + tid;
-      const int kv = idx / (DH / 8);
-      const int slot = idx % (DH / 8);
-      const int kvg = k0 + kv;
-      s16x8 kr = s16x8{}, vr = s16x8{};
-      if (kvg < L) {
-        kr = *reinterpret_cast<const s16x8*>(
-            &Kp[(long long)kvg * skS + slot * 8]);
-        vr = *reinterpret_cast<const s16x8*>(
-            &Vp[(long long)kvg * svS + slot * 8]);
-      }
-      *reinterpret_cast<__attribute__((address_space(3))) s16x8*>(
-          (__attribute__((address_space(3))) bf16*)&kb[koff<DH>(kv, slot * 8)]) = kr;
-      *reinterpret_cast<__attribute__((address_space(3))) s16x8*>(
-          (__attribute__((address_space(3))) bf16*)&vb[koff<DH>(kv, slot * 8)]) = vr;
+      const int kv = chunk_row<DH>(c * THREADS + tid);
+      const int slot = chunk_slot<DH>(c * THREADS + tid);
+      s16x8 kr, vr;
+      load_chunk2<DH>(c * THREADS + tid, k0, L, Kp, skS, Vp, svS, kr, vr);
+      lds_store128(&kb[koff<DH>(kv, slot * 8)], kr);
+      lds_store128(&vb[koff<DH>(kv, slot * 8)], vr);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         ktb[voff(slot * 8 + j, kv)] = ((const bf16*)&kr)[j];
@@ -492,23 +502,7 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
         ds[r] = p * (dpacc[r] - delta_q) * scale;
       }
 #pragma unroll
-      for (int hk = 0; hk < 2; ++hk) {
-        const int o8 = hk * 8;
-        unsigned int A = pk_bf16(ds[o8 + 0], ds[o8 + 1]);
-        unsigned int B = pk_bf16(ds[o8 + 2], ds[o8 + 3]);
-        unsigned int C = pk_bf16(ds[o8 + 4], ds[o8 + 5]);
-        unsigned int D = pk_bf16(ds[o8 + 6], ds[o8 + 7]);
-        {
-          u32x2 r = __builtin_amdgcn_permlane32_swap(A, C, false, false);
-          A = r[0]; C = r[1];
-        }
-        {
-          u32x2 r = __builtin_amdgcn_permlane32_swap(B, D, false, false);
-          B = r[0]; D = r[1];
-        }
-        unsigned int dw[4] = {A, B, C, D};
-        dsf[st][hk] = *reinterpret_cast<const s16x8*>(dw);
-      }
+      for (int hk = 0; hk < 2; ++hk) dsf[st][hk] = pack_frag(ds + hk * 8);
     }
     // dQ^T += K^T x dS^T
 #pragma unroll
@@ -525,21 +519,10 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
   }
 
   if (!qvalid) {
-    if (VARLEN && qg < S) store_zero_row<DH>(dQp + (long long)qg * dqS, hi);
+    if (VARLEN && qg < S) store_zero_row<DH>(dQp + (long long)qg * sdqS, hi);
     return;
   }
-  bf16* dqrow = dQp + (long long)qg * dqS;
-#pragma unroll
-  for (int db = 0; db < DB; ++db)
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const int d0 = db * 32 + qd * 8 + hi * 4;
-      const unsigned int w0 =
-          pk_bf16(dq_acc[db][qd * 4 + 0], dq_acc[db][qd * 4 + 1]);
-      const unsigned int w1 =
-          pk_bf16(dq_acc[db][qd * 4 + 2], dq_acc[db][qd * 4 + 3]);
-      *reinterpret_cast<u32x2*>(&dqrow[d0]) = u32x2{w0, w1};
-    }
+  store_row<DH>(dQp + (long long)qg * sdqS, dq_acc, hi);
 }
 
 // dK/dV kernel: kv-tile-major; each wave owns 32 kv rows of a 128-kv block
@@ -547,8 +530,6 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dq_kernel(
 // S = mfma(Q, K), dP = mfma(dO, V) — all row-major reads; P/dS fragments
 // via the same half-swap; dV^T += mfma(dO^T, P), dK^T += mfma(Q^T, dS).
 // Outputs are PER-Q-HEAD (GQA callers group-sum), so no atomics.
-constexpr int KVBB = 128;           // kv rows per block (32 per wave)
-
 template <int DH, bool CAUSAL, bool VARLEN>
 __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
@@ -559,16 +540,16 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
     long long sqB, long long sqS, long long sqH,
     long long skB, long long skS, long long skH,
     long long svB, long long svS, long long svH,
-    long long doB, long long doS, long long doH,
-    long long dkB, long long dkS, long long dkH,
-    long long dvB, long long dvS, long long dvH,
-    typename LenArg<VARLEN>::type lens) {
+    long long sdoB, long long sdoS, long long sdoH,
+    long long sdkB, long long sdkS, long long sdkH,
+    long long sdvB, long long sdvS, long long sdvH,
+    Lens<VARLEN> lens) {
   constexpr int F = DH / 16;
   constexpr int DB = DH / 32;
 
   // K rows [128][DH] | V rows [128][DH] | Q [32][DH] | dO [32][DH] |
   // Q^T [DH][32] | dO^T [DH][32]
-  __shared__ bf16 lds[2 * KVBB * DH + 2 * 32 * DH + 2 * DH * 32];
+  __shared__ bf16 lds[dkv_lds_bytes(DH) / sizeof(bf16)];
   bf16* kb = lds;
   bf16* vb = lds + KVBB * DH;
   bf16* qb = lds + 2 * KVBB * DH;
@@ -588,9 +569,9 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
   const bf16* Qp = Q + b * sqB + h * sqH;
   const bf16* Kp = K + b * skB + kvh * skH;
   const bf16* Vp = V + b * svB + kvh * svH;
-  const bf16* dOp = dO + b * doB + h * doH;
-  bf16* dKp = dK + b * dkB + h * dkH;
-  bf16* dVp = dV + b * dvB + h * dvH;
+  const bf16* dOp = dO + b * sdoB + h * sdoH;
+  bf16* dKp = dK + b * sdkB + h * sdkH;
+  bf16* dVp = dV + b * sdvB + h * sdvH;
 
   const int kv0 = blockIdx.x * KVBB;
   const int kv_w = kv0 + wid * 32;            // wave's kv base
@@ -598,32 +579,27 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
   const int L = live_len<VARLEN>(lens, b, S);
   if (VARLEN && kv0 >= L) {       // dead block: whole block, before staging
     if (kvg < S) {
-      store_zero_row<DH>(dKp + (long long)kvg * dkS, hi);
-      store_zero_row<DH>(dVp + (long long)kvg * dvS, hi);
+      store_zero_row<DH>(dKp + (long long)kvg * sdkS, hi);
+      store_zero_row<DH>(dVp + (long long)kvg * sdvS, hi);
     }
     return;
   }
   const bool kvalid = kvg < L;
 
   // ---- stage block-persistent K/V row images (swizzled)
-  {
-    const int nchunk = KVBB * DH / 8;         // 16-B chunks
-    for (int idx = tid; idx < nchunk; idx += THREADS) {
-      const int kv = idx / (DH / 8);
-      const int slot = idx % (DH / 8);
-      const int g = kv0 + kv;
-      s16x8 kr = s16x8{}, vr = s16x8{};
-      if (g < L) {
-        kr = *reinterpret_cast<const s16x8*>(
-            &Kp[(long long)g * skS + slot * 8]);
-        vr = *reinterpret_cast<const s16x8*>(
-            &Vp[(long long)g * svS + slot * 8]);
-      }
-      *reinterpret_cast<__attribute__((address_space(3))) s16x8*>(
-          (__attribute__((address_space(3))) bf16*)&kb[koff<DH>(kv, slot * 8)]) = kr;
-      *reinterpret_cast<__attribute__((address_space(3))) s16x8*>(
-          (__attribute__((address_space(3))) bf16*)&vb[koff<DH>(kv, slot * 8)]) = vr;
+  // (spelled out like the Q / dO loop below: through load_chunk2 the zeroing
+  // of kr and vr swaps places and the main loop is scheduled differently)
+  for (int idx = tid; idx < KVBB * DH / 8; idx += THREADS) {
+    const int kv = idx / (DH / 8);
+    const int slot = idx % (DH / 8);
+    const int g = kv0 + kv;
+    s16x8 kr = s16x8{}, vr = s16x8{};
+    if (g < L) {
+      kr = *reinterpret_cast<const s16x8*>(&Kp[(long long)g * skS + slot * 8]);
+      vr = *reinterpret_cast<const s16x8*>(&Vp[(long long)g * svS + slot * 8]);
     }
+    lds_store128(&kb[koff<DH>(kv, slot * 8)], kr);
+    lds_store128(&vb[koff<DH>(kv, slot * 8)], vr);
   }
 
   f32x16 dv_acc[DB] = {}, dk_acc[DB] = {};
@@ -633,7 +609,10 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
 
   for (int qt = qt0; qt < nqt; ++qt) {
     const int q0t = qt * 32;
-    // ---- stage Q/dO row images + transposes (32 rows)
+    // ---- stage Q/dO row images + transposes (32 rows). Spelled out: with
+    // chunk_row / chunk_slot, load_chunk2 or qtoff in this loop the compiler
+    // keeps 8 transposed-write addresses live where this text keeps 4 (4 more
+    // VGPRs at dh 32 and 64, other instruction counts)
     __syncthreads();
     {
       const int nchunk = 32 * DH / 8;
@@ -646,12 +625,10 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
           qr16 = *reinterpret_cast<const s16x8*>(
               &Qp[(long long)g * sqS + slot * 8]);
           dor16 = *reinterpret_cast<const s16x8*>(
-              &dOp[(long long)g * doS + slot * 8]);
+              &dOp[(long long)g * sdoS + slot * 8]);
         }
-        *reinterpret_cast<__attribute__((address_space(3))) s16x8*>(
-            (__attribute__((address_space(3))) bf16*)&qb[koff<DH>(qr, slot * 8)]) = qr16;
-        *reinterpret_cast<__attribute__((address_space(3))) s16x8*>(
-            (__attribute__((address_space(3))) bf16*)&dob[koff<DH>(qr, slot * 8)]) = dor16;
+        lds_store128(&qb[koff<DH>(qr, slot * 8)], qr16);
+        lds_store128(&dob[koff<DH>(qr, slot * 8)], dor16);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int d = slot * 8 + j;
@@ -696,47 +673,17 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
 #pragma unroll
     for (int hk = 0; hk < 2; ++hk) {
       const int o8 = hk * 8;
-      unsigned int A = pk_bf16(pv[o8 + 0], pv[o8 + 1]);
-      unsigned int B = pk_bf16(pv[o8 + 2], pv[o8 + 3]);
-      unsigned int C = pk_bf16(pv[o8 + 4], pv[o8 + 5]);
-      unsigned int D = pk_bf16(pv[o8 + 6], pv[o8 + 7]);
-      {
-        u32x2 r = __builtin_amdgcn_permlane32_swap(A, C, false, false);
-        A = r[0]; C = r[1];
-      }
-      {
-        u32x2 r = __builtin_amdgcn_permlane32_swap(B, D, false, false);
-        B = r[0]; D = r[1];
-      }
-      unsigned int dw[4] = {A, B, C, D};
-      pfr[hk] = *reinterpret_cast<const s16x8*>(dw);
-
-      unsigned int A2 = pk_bf16(ds[o8 + 0], ds[o8 + 1]);
-      unsigned int B2 = pk_bf16(ds[o8 + 2], ds[o8 + 3]);
-      unsigned int C2 = pk_bf16(ds[o8 + 4], ds[o8 + 5]);
-      unsigned int D2 = pk_bf16(ds[o8 + 6], ds[o8 + 7]);
-      {
-        u32x2 r = __builtin_amdgcn_permlane32_swap(A2, C2, false, false);
-        A2 = r[0]; C2 = r[1];
-      }
-      {
-        u32x2 r = __builtin_amdgcn_permlane32_swap(B2, D2, false, false);
-        B2 = r[0]; D2 = r[1];
-      }
-      unsigned int dw2[4] = {A2, B2, C2, D2};
-      dsfr[hk] = *reinterpret_cast<const s16x8*>(dw2);
+      pfr[hk] = pack_frag(pv + o8);
+      dsfr[hk] = pack_frag(ds + o8);
     }
     // dV^T += dO^T x P ; dK^T += Q^T x dS
 #pragma unroll
     for (int db = 0; db < DB; ++db)
 #pragma unroll
       for (int hk = 0; hk < 2; ++hk) {
-        const int d = db * 32 + lkv;
-        const int qcol = hk * 16 + hi * 8;
-        const s16x8 adot = lds128(
-            &dotb[d * 32 + ((((qcol >> 3) ^ d) & 3) << 3) + (qcol & 7)]);
-        const s16x8 aqt = lds128(
-            &qtb[d * 32 + ((((qcol >> 3) ^ d) & 3) << 3) + (qcol & 7)]);
+        const int off = qtoff(db * 32 + lkv, hk * 16 + hi * 8);
+        const s16x8 adot = lds128(&dotb[off]);
+        const s16x8 aqt = lds128(&qtb[off]);
         dv_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
             adot, pfr[hk], dv_acc[db], 0, 0, 0);
         dk_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
@@ -746,13 +693,15 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
 
   if (!kvalid) {
     if (VARLEN && kvg < S) {      // padded row of a live block
-      store_zero_row<DH>(dKp + (long long)kvg * dkS, hi);
-      store_zero_row<DH>(dVp + (long long)kvg * dvS, hi);
+      store_zero_row<DH>(dKp + (long long)kvg * sdkS, hi);
+      store_zero_row<DH>(dVp + (long long)kvg * sdvS, hi);
     }
     return;
   }
-  bf16* dkrow = dKp + (long long)kvg * dkS;
-  bf16* dvrow = dVp + (long long)kvg * dvS;
+  bf16* dkrow = dKp + (long long)kvg * sdkS;
+  bf16* dvrow = dVp + (long long)kvg * sdvS;
+  // store_row twice, run by run, spelled out: two calls in sequence cost
+  // VARLEN 20+ instructions, and any helper here reorders the main loop
 #pragma unroll
   for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -771,132 +720,94 @@ __global__ __launch_bounds__(THREADS) void flash_bwd_dkv_kernel(
     }
 }
 
+// Host dispatch: f(dh, causal, varlen) gets the three as integral constants,
+// varlen being "a has seq_lens"; nothing runs for a route that refuses.
+template <typename F>
+void dispatch(const FlashRoute& rt, int DH, bool causal, const FlashArgs& a,
+              F&& f) {
+  if (!rt.eligible) throw std::runtime_error(rt.refusal);
+  dispatch2(causal, a.seq_lens != nullptr, [&](auto cz, auto vl) {
+    if (DH == 32) f(std::integral_constant<int, 32>{}, cz, vl);
+    else if (DH == 64) f(std::integral_constant<int, 64>{}, cz, vl);
+    else f(std::integral_constant<int, 128>{}, cz, vl);
+  });
+}
+
+// seq_lens for VARLEN, the empty struct for the dense instantiations
+template <bool VL> Lens<VL> lens_arg(const int* seq_lens) {
+  if constexpr (VL) return seq_lens; else return NoLens{};
+}
+
 }  // namespace fa
 
-#include "launchers.h"
+// Each launcher launches the grid the route names, with the strides of the
+// problem's views. a.seq_lens == nullptr launches the dense instantiations
+// (empty-struct last argument), else the VARLEN ones on the same grid.
 
-// seq_lens == nullptr launches the dense instantiations (empty-struct last
-// argument); otherwise the VARLEN ones on the same grid.
-bool launch_flash_fwd(const void* Q, const void* K, const void* V, void* O,
-                      float* LSE, int B, int S, int H, int G, int DH,
-                      float scale, bool causal,
-                      const long long* qs, const long long* ks,
-                      const long long* vs, const long long* os,
-                      const int* seq_lens, hipStream_t s) {
-  if (DH != 32 && DH != 64 && DH != 128) return false;
-  dim3 grid((S + fa::QB - 1) / fa::QB, B * H);
-#define FA_CALL(DHV, CZ, VL, LENS)                                            \
-  hipLaunchKernelGGL((fa::flash_fwd_kernel<DHV, CZ, VL>), grid,               \
-                     dim3(fa::THREADS), 0, s, (const bf16*)Q, (const bf16*)K, \
-                     (const bf16*)V, (bf16*)O, LSE, S, H, G, scale,           \
-                     qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],                \
-                     vs[0], vs[1], vs[2], os[0], os[1], os[2], LENS)
-#define FA_DH(DHV)                                                            \
-  do {                                                                        \
-    if (seq_lens) {                                                           \
-      if (causal) FA_CALL(DHV, true, true, seq_lens);                         \
-      else FA_CALL(DHV, false, true, seq_lens);                               \
-    } else {                                                                  \
-      if (causal) FA_CALL(DHV, true, false, fa::NoLens{});                    \
-      else FA_CALL(DHV, false, false, fa::NoLens{});                          \
-    }                                                                         \
-  } while (0)
-  if (DH == 32) FA_DH(32);
-  else if (DH == 64) FA_DH(64);
-  else FA_DH(128);
-#undef FA_DH
-#undef FA_CALL
-  return true;
+void launch_flash_fwd(const FlashRoute& rt, const FlashProblem& p,
+                      const FlashArgs& a, float scale, hipStream_t s) {
+  const AttnView *q = &p.view[kQ], *k = &p.view[kK], *v = &p.view[kV],
+                 *o = &p.view[kO];
+  fa::dispatch(rt, p.DH, p.causal, a, [&](auto dh, auto cz, auto vl) {
+    constexpr int DH = decltype(dh)::value;
+    constexpr bool CZ = decltype(cz)::value, VL = decltype(vl)::value;
+    hipLaunchKernelGGL((fa::flash_fwd_kernel<DH, CZ, VL>),
+                       dim3(rt.grid_fwd[0], rt.grid_fwd[1]), dim3(fa::THREADS),
+                       0, s, (const bf16*)a.q, (const bf16*)a.k,
+                       (const bf16*)a.v, (bf16*)a.o, a.lse, p.S, p.H, rt.G,
+                       scale, q->sB, q->sS, q->sH, k->sB, k->sS, k->sH, v->sB,
+                       v->sS, v->sH, o->sB, o->sS, o->sH,
+                       fa::lens_arg<VL>(a.seq_lens));
+  });
 }
 
-void launch_flash_delta(const void* dO, const void* O, float* delta,
-                        int B, int S, int H, int DH,
-                        const long long* dos, const long long* os,
-                        const int* seq_lens, hipStream_t s) {
-  dim3 grid((S + 3) / 4, B * H);
-#define FD_CALL(DHV, VL, LENS)                                               \
-  hipLaunchKernelGGL((fa::flash_delta_kernel<DHV, VL>), grid, dim3(256), 0,  \
-                     s, (const bf16*)dO, (const bf16*)O, delta, S, H,        \
-                     dos[0], dos[1], dos[2], os[0], os[1], os[2], LENS)
-#define FD_DH(DHV)                                                           \
-  do {                                                                       \
-    if (seq_lens) FD_CALL(DHV, true, seq_lens);                              \
-    else FD_CALL(DHV, false, fa::NoLens{});                                  \
-  } while (0)
-  if (DH == 32) FD_DH(32);
-  else if (DH == 64) FD_DH(64);
-  else FD_DH(128);
-#undef FD_DH
-#undef FD_CALL
+void launch_flash_delta(const FlashRoute& rt, const FlashProblem& p,
+                        const FlashArgs& a, hipStream_t s) {
+  const AttnView *dO = &p.view[kDout], *o = &p.view[kO];
+  fa::dispatch(rt, p.DH, false, a, [&](auto dh, auto, auto vl) {
+    constexpr int DH = decltype(dh)::value;
+    constexpr bool VL = decltype(vl)::value;
+    hipLaunchKernelGGL((fa::flash_delta_kernel<DH, VL>),
+                       dim3(rt.grid_delta[0], rt.grid_delta[1]),
+                       dim3(fa::THREADS), 0, s, (const bf16*)a.dout,
+                       (const bf16*)a.o, a.delta, p.S, p.H, dO->sB, dO->sS,
+                       dO->sH, o->sB, o->sS, o->sH,
+                       fa::lens_arg<VL>(a.seq_lens));
+  });
 }
 
-bool launch_flash_bwd_dq(const void* Q, const void* K, const void* V,
-                         const void* dO, const float* LSE, const float* DELTA,
-                         void* dQ, int B, int S, int H, int G, int DH,
-                         float scale, bool causal,
-                         const long long* qs, const long long* ks,
-                         const long long* vs, const long long* dos,
-                         const long long* dqs, const int* seq_lens,
-                         hipStream_t s) {
-  if (DH != 32 && DH != 64 && DH != 128) return false;
-  dim3 grid((S + fa::QB - 1) / fa::QB, B * H);
-#define DQ_CALL(DHV, CZ, VL, LENS)                                            \
-  hipLaunchKernelGGL((fa::flash_bwd_dq_kernel<DHV, CZ, VL>), grid,            \
-                     dim3(fa::THREADS), 0, s, (const bf16*)Q, (const bf16*)K, \
-                     (const bf16*)V, (const bf16*)dO, LSE, DELTA, (bf16*)dQ,  \
-                     S, H, G, scale, qs[0], qs[1], qs[2], ks[0], ks[1],       \
-                     ks[2], vs[0], vs[1], vs[2], dos[0], dos[1], dos[2],      \
-                     dqs[0], dqs[1], dqs[2], LENS)
-#define DQ_DH(DHV)                                                            \
-  do {                                                                        \
-    if (seq_lens) {                                                           \
-      if (causal) DQ_CALL(DHV, true, true, seq_lens);                         \
-      else DQ_CALL(DHV, false, true, seq_lens);                               \
-    } else {                                                                  \
-      if (causal) DQ_CALL(DHV, true, false, fa::NoLens{});                    \
-      else DQ_CALL(DHV, false, false, fa::NoLens{});                          \
-    }                                                                         \
-  } while (0)
-  if (DH == 32) DQ_DH(32);
-  else if (DH == 64) DQ_DH(64);
-  else DQ_DH(128);
-#undef DQ_DH
-#undef DQ_CALL
-  return true;
+void launch_flash_bwd_dq(const FlashRoute& rt, const FlashProblem& p,
+                         const FlashArgs& a, float scale, hipStream_t s) {
+  const AttnView *q = &p.view[kQ], *k = &p.view[kK], *v = &p.view[kV],
+                 *dO = &p.view[kDout], *dq = &p.view[kDq];
+  fa::dispatch(rt, p.DH, p.causal, a, [&](auto dh, auto cz, auto vl) {
+    constexpr int DH = decltype(dh)::value;
+    constexpr bool CZ = decltype(cz)::value, VL = decltype(vl)::value;
+    hipLaunchKernelGGL((fa::flash_bwd_dq_kernel<DH, CZ, VL>),
+                       dim3(rt.grid_dq[0], rt.grid_dq[1]), dim3(fa::THREADS),
+                       0, s, (const bf16*)a.q, (const bf16*)a.k,
+                       (const bf16*)a.v, (const bf16*)a.dout, a.lse, a.delta,
+                       (bf16*)a.dq, p.S, p.H, rt.G, scale, q->sB, q->sS, q->sH,
+                       k->sB, k->sS, k->sH, v->sB, v->sS, v->sH, dO->sB,
+                       dO->sS, dO->sH, dq->sB, dq->sS, dq->sH,
+                       fa::lens_arg<VL>(a.seq_lens));
+  });
 }
 
-bool launch_flash_bwd_dkv(const void* Q, const void* K, const void* V,
-                          const void* dO, const float* LSE, const float* DELTA,
-                          void* dK, void* dV, int B, int S, int H, int G,
-                          int DH, float scale, bool causal,
-                          const long long* qs, const long long* ks,
-                          const long long* vs, const long long* dos,
-                          const long long* dks, const long long* dvs,
-                          const int* seq_lens, hipStream_t s) {
-  if (DH != 32 && DH != 64 && DH != 128) return false;
-  dim3 grid((S + fa::KVBB - 1) / fa::KVBB, B * H);
-#define DKV_CALL(DHV, CZ, VL, LENS)                                           \
-  hipLaunchKernelGGL((fa::flash_bwd_dkv_kernel<DHV, CZ, VL>), grid,           \
-                     dim3(fa::THREADS), 0, s, (const bf16*)Q, (const bf16*)K, \
-                     (const bf16*)V, (const bf16*)dO, LSE, DELTA, (bf16*)dK,  \
-                     (bf16*)dV, S, H, G, scale, qs[0], qs[1], qs[2], ks[0],   \
-                     ks[1], ks[2], vs[0], vs[1], vs[2], dos[0], dos[1],       \
-                     dos[2], dks[0], dks[1], dks[2], dvs[0], dvs[1], dvs[2],  \
-                     LENS)
-#define DKV_DH(DHV)                                                           \
-  do {                                                                        \
-    if (seq_lens) {                                                           \
-      if (causal) DKV_CALL(DHV, true, true, seq_lens);                        \
-      else DKV_CALL(DHV, false, true, seq_lens);                              \
-    } else {                                                                  \
-      if (causal) DKV_CALL(DHV, true, false, fa::NoLens{});                   \
-      else DKV_CALL(DHV, false, false, fa::NoLens{});                         \
-    }                                                                         \
-  } while (0)
-  if (DH == 32) DKV_DH(32);
-  else if (DH == 64) DKV_DH(64);
-  else DKV_DH(128);
-#undef DKV_DH
-#undef DKV_CALL
-  return true;
+void launch_flash_bwd_dkv(const FlashRoute& rt, const FlashProblem& p,
+                          const FlashArgs& a, float scale, hipStream_t s) {
+  const AttnView *q = &p.view[kQ], *k = &p.view[kK], *v = &p.view[kV],
+                 *dO = &p.view[kDout], *dk = &p.view[kDk], *dv = &p.view[kDv];
+  fa::dispatch(rt, p.DH, p.causal, a, [&](auto dh, auto cz, auto vl) {
+    constexpr int DH = decltype(dh)::value;
+    constexpr bool CZ = decltype(cz)::value, VL = decltype(vl)::value;
+    hipLaunchKernelGGL((fa::flash_bwd_dkv_kernel<DH, CZ, VL>),
+                       dim3(rt.grid_dkv[0], rt.grid_dkv[1]), dim3(fa::THREADS),
+                       0, s, (const bf16*)a.q, (const bf16*)a.k,
+                       (const bf16*)a.v, (const bf16*)a.dout, a.lse, a.delta,
+                       (bf16*)a.dk, (bf16*)a.dv, p.S, p.H, rt.G, scale, q->sB,
+                       q->sS, q->sH, k->sB, k->sS, k->sH, v->sB, v->sS, v->sH,
+                       dO->sB, dO->sS, dO->sH, dk->sB, dk->sS, dk->sH, dv->sB,
+                       dv->sS, dv->sH, fa::lens_arg<VL>(a.seq_lens));
+  });
 }

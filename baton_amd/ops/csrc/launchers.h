@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "attn_route.h"
 #include "conv_route.h"
 #include "gemm_plan.h"
 #include "gemm_strides.h"
@@ -148,7 +149,7 @@ bool launch_gemm_nt_slab(const GemmPlan& pl, const void* A, const void* B,
 // attention.hip — row softmax with scale + optional causal mask and optional
 // per-sequence key lengths: kv_len is nullptr, or device int32 lengths where
 // rows_per_len consecutive rows share one entry and r % q_period is a row's
-// query position
+// query position. Kernel and grid are softmax_route's (attn_route.h).
 void launch_softmax_fwd(bool is_bf16, const void* x, void* y, long long R,
                         int C, float scale, int causal_seq, const int* kv_len,
                         long long rows_per_len, int q_period, hipStream_t s);
@@ -173,36 +174,25 @@ void launch_transpose(bool is_bf16, const void* in, void* out, int R, int C,
 void launch_colsum(bool is_bf16, const void* x, float* out, long long R, int C,
                    hipStream_t s);
 
-// flash.hip — fused flash attention (bf16, DH in {32,64,128}); strides in
-// elements as [batch, seq, head] triples; returns false if DH unsupported.
-// seq_lens: nullptr for full rows (the dense kernels), or B device int32
-// lengths of right-padded sequences (the length-aware instantiations).
-bool launch_flash_fwd(const void* Q, const void* K, const void* V, void* O,
-                      float* LSE, int B, int S, int H, int G, int DH,
-                      float scale, bool causal,
-                      const long long* qs, const long long* ks,
-                      const long long* vs, const long long* os,
-                      const int* seq_lens, hipStream_t s);
-void launch_flash_delta(const void* dO, const void* O, float* delta,
-                        int B, int S, int H, int DH,
-                        const long long* dos, const long long* os,
-                        const int* seq_lens, hipStream_t s);
-bool launch_flash_bwd_dq(const void* Q, const void* K, const void* V,
-                         const void* dO, const float* LSE, const float* DELTA,
-                         void* dQ, int B, int S, int H, int G, int DH,
-                         float scale, bool causal,
-                         const long long* qs, const long long* ks,
-                         const long long* vs, const long long* dos,
-                         const long long* dqs, const int* seq_lens,
-                         hipStream_t s);
-bool launch_flash_bwd_dkv(const void* Q, const void* K, const void* V,
-                          const void* dO, const float* LSE, const float* DELTA,
-                          void* dK, void* dV, int B, int S, int H, int G,
-                          int DH, float scale, bool causal,
-                          const long long* qs, const long long* ks,
-                          const long long* vs, const long long* dos,
-                          const long long* dks, const long long* dvs,
-                          const int* seq_lens, hipStream_t s);
+// flash.hip — fused flash attention. Each launcher launches the grid the
+// route (flash_route of the problem, attn_route.h) names, with the strides of
+// the problem's views, and throws on a route that is not eligible. seq_lens:
+// nullptr (the dense kernels), or B device int32 lengths of right-padded
+// sequences (the length-aware instantiations).
+struct FlashArgs {
+  const void *q, *k, *v, *dout;   // dout, delta, dq, dk, dv: backward only
+  void *o, *dq, *dk, *dv;
+  float *lse, *delta;
+  const int* seq_lens;
+};
+void launch_flash_fwd(const FlashRoute& rt, const FlashProblem& p,
+                      const FlashArgs& a, float scale, hipStream_t s);
+void launch_flash_delta(const FlashRoute& rt, const FlashProblem& p,
+                        const FlashArgs& a, hipStream_t s);
+void launch_flash_bwd_dq(const FlashRoute& rt, const FlashProblem& p,
+                         const FlashArgs& a, float scale, hipStream_t s);
+void launch_flash_bwd_dkv(const FlashRoute& rt, const FlashProblem& p,
+                          const FlashArgs& a, float scale, hipStream_t s);
 
 // conv8.hip — deep-pipelined 256x256 8-wave conv fwd / stride-1 dgrad
 // (bf16; p.op picks). b is w for fwd, the transposed w_t for dgrad.

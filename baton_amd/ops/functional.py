@@ -929,22 +929,11 @@ def _attn_core_bwd(ops, q, k, v, probs, do, dq, dk_qh, dv_qh):
 
 
 def _flash_eligible(q, k, v) -> bool:
-    """Fused flash path: bf16, dh in {32,64,128}, contiguous head_dim, and
-    views the kernels' 16-byte vector accesses can address (16-byte aligned
-    base, outer strides multiples of 8 elements) — flash_fwd refuses anything
-    else. BATON_NO_FLASH=1 forces the materialized-scores path (A/B runs)."""
-    import os
-
-    def aligned(t):
-        return (t.stride(-1) == 1 and t.data_ptr() % 16 == 0
-                and all(s % 8 == 0 for s in t.stride()[:-1]))
-
-    return (
-        q.dtype == torch.bfloat16
-        and q.shape[-1] in (32, 64, 128)
-        and aligned(q) and aligned(k) and aligned(v)
-        and os.environ.get("BATON_NO_FLASH", "0") != "1"
-    )
+    """Fused flash path: what flash_route (csrc/attn_route.h), the gate
+    flash_fwd refuses from, accepts for these three views. BATON_NO_FLASH=1
+    forces the materialized-scores path (A/B runs); the header reads none."""
+    return (os.environ.get("BATON_NO_FLASH", "0") != "1"
+            and require_hip().flash_eligible(q, k, v))
 
 
 class AttnPackedFn(torch.autograd.Function):

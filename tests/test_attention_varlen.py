@@ -185,10 +185,12 @@ def raw_run(name):
     assert BF._flash_eligible(qd, kd, vd)
     lens = lens_tensor(c)
     po, o = FE.canary_output(c)
+    outs = [FE.canary_output(c) for _ in range(3)]
+    FE.check_route(c, varlen=True, q=qd, k=kd, v=vd, o=o, dout=dod,
+                   dq=outs[0][1], dk=outs[1][1], dv=outs[2][1])
     ret, lse = OPS.flash_fwd(qd, kd, vd, o, c["causal"], lens)
     assert ret.data_ptr() == o.data_ptr()
     assert lse.dtype == FP32 and tuple(lse.shape) == (c["B"] * c["h"], c["S"])
-    outs = [FE.canary_output(c) for _ in range(3)]
     OPS.flash_bwd(qd, kd, vd, o, dod, lse, outs[0][1], outs[1][1], outs[2][1],
                   c["causal"], lens)
     res = dict(o=FE.check_canary("o", c, po), lse=lse.cpu())

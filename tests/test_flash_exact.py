@@ -286,6 +286,24 @@ def check_canary(tag, c, parent):
     return p[:, :c["S"], :, :c["dh"]]
 
 
+def check_route(c, varlen=False, **views):
+    """flash_route (csrc/attn_route.h, what flash_fwd / flash_bwd refuse and
+    launch from) takes the case with these views (name -> tensor; the others
+    contiguous) and names the expected grids, G and LDS sizes."""
+    B, S, h, dh = c["B"], c["S"], c["h"], c["dh"]
+    d = OPS.flash_route(B, S, h, c["kvh"], dh, causal=c["causal"],
+                        varlen=varlen, bwd=True,
+                        views={n: [*t.stride(), t.data_ptr() % 16]
+                               for n, t in views.items()})
+    assert d["eligible"], d["refusal"]
+    tiles = (-(-S // 128), B * h)
+    assert d["grid_fwd"] == d["grid_dq"] == d["grid_dkv"] == tiles
+    assert d["grid_delta"] == (-(-S // 4), B * h)
+    assert d["G"] == h // c["kvh"]
+    assert (d["lds_fwd"], d["lds_dq"], d["lds_dkv"]) == \
+        (512 * dh, 384 * dh, 768 * dh)
+
+
 @functools.lru_cache(maxsize=None)
 def raw_run(name):
     """flash_fwd then flash_bwd on the case's views; CPU copies of o, lse,
@@ -295,10 +313,12 @@ def raw_run(name):
     qd, kd, vd, dod = padded_inputs(c, q, k, v, dout)
     assert BF._flash_eligible(qd, kd, vd)
     po, o = canary_output(c)
+    outs = [canary_output(c) for _ in range(3)]
+    check_route(c, q=qd, k=kd, v=vd, o=o, dout=dod, dq=outs[0][1],
+                dk=outs[1][1], dv=outs[2][1])
     ret, lse = OPS.flash_fwd(qd, kd, vd, o, c["causal"])
     assert ret.data_ptr() == o.data_ptr()
     assert lse.dtype == FP32 and tuple(lse.shape) == (c["B"] * c["h"], c["S"])
-    outs = [canary_output(c) for _ in range(3)]
     OPS.flash_bwd(qd, kd, vd, o, dod, lse, outs[0][1], outs[1][1], outs[2][1],
                   c["causal"])
     res = dict(o=check_canary("o", c, po), lse=lse.cpu())
@@ -375,20 +395,35 @@ def test_attention_bshd_gqa_group_sum():
 @pytest.mark.gpu
 def test_flash_gate(monkeypatch):
     monkeypatch.delenv("BATON_NO_FLASH", raising=False)
+
+    def eligible(q, k, v, refusal=None):
+        """_flash_eligible, which is false exactly when flash_fwd refuses
+        the views, with flash_route's text ``refusal`` (both are its
+        answer)."""
+        e = BF._flash_eligible(q, k, v)
+        assert e == (refusal is None)
+        o = torch.empty(q.shape, dtype=BF16, device=DEV)
+        if e:
+            OPS.flash_fwd(q, k, v, o, False)
+        else:
+            with pytest.raises(RuntimeError, match=refusal):
+                OPS.flash_fwd(q, k, v, o, False)
+        return e
+
     ok = torch.zeros(1, 32, 2, 32, dtype=BF16, device=DEV)
-    assert BF._flash_eligible(ok, ok, ok)
+    assert eligible(ok, ok, ok)
     f32 = torch.randn(1, 32, 2, 32, device=DEV)
-    assert not BF._flash_eligible(f32, f32, f32)
+    assert not eligible(f32, f32, f32, "q must be a bf16 GPU tensor")
     dh48 = torch.zeros(1, 32, 2, 48, dtype=BF16, device=DEV)
-    assert not BF._flash_eligible(dh48, dh48, dh48)
+    assert not eligible(dh48, dh48, dh48, "unsupported head_dim 48")
     # misaligned views take the legacy path instead of raising: a base
     # pointer 8 bytes in, and a head stride of dh + 4
     off = torch.zeros(1 * 32 * 2 * 32 + 4, dtype=BF16, device=DEV)[4:].view(
         1, 32, 2, 32)
-    assert not BF._flash_eligible(off, ok, ok)
-    assert not BF._flash_eligible(ok, off, ok)
+    assert not eligible(off, ok, ok, "q must start on a 16-byte boundary")
+    assert not eligible(ok, off, ok, "k must start on a 16-byte boundary")
     odd = torch.zeros(1, 32, 2, 36, dtype=BF16, device=DEV)[..., :32]
-    assert not BF._flash_eligible(ok, ok, odd)
+    assert not eligible(ok, ok, odd, "v strides must be multiples of 8")
     monkeypatch.setenv("BATON_NO_FLASH", "1")
     assert not BF._flash_eligible(ok, ok, ok)
     monkeypatch.delenv("BATON_NO_FLASH")

@@ -85,9 +85,10 @@ def case_id(c):
 
 
 def route(R, C, dtype):
-    """The launcher's and kernels' gates: C <= 1024 picks the wave kernel
-    (4 rows per block), 16-byte vectors need C % V == 0 and C >= 64 V, and
-    more than kMaxGrid blocks grid-stride."""
+    """A model of softmax_route (csrc/attn_route.h), which the launchers
+    and kernels execute and tests/test_attention_route.py holds equal to this:
+    C <= 1024 picks the wave kernel (4 rows per block), 16-byte vectors need
+    C % V == 0 and C >= 64 V, and more than kMaxGrid blocks grid-stride."""
     V = 8 if dtype == BF16 else 4
     wave = C <= 1024
     blocks = (R + 3) // 4 if wave else R
@@ -99,6 +100,9 @@ def check_route(R, C, dtype):
     kernel, vec_bf16, vec_fp32, trip = SHAPES[(R, C)]
     want = (kernel, vec_bf16 if dtype == BF16 else vec_fp32, trip)
     assert route(R, C, dtype) == want, (R, C, dtype, route(R, C, dtype), want)
+    if torch.cuda.is_available():   # what the launchers execute
+        d = OPS.softmax_route(R, C, dtype == BF16)
+        assert (d["kernel"], d["vec"], d["capped"]) == want, (R, C, dtype, d)
 
 
 def keep_mask(R, C, causal):

@@ -176,6 +176,132 @@ void adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
               zero_grad ? 1 : 0, stream());
 }
 
+// Clipping, the non-finite skip and decoupled decay (optim.hip). Everything
+// these ops refuse is refused here, before any launch, by argument name.
+
+namespace {
+
+// p / g / m / v of the new ops: on the GPU, contiguous, 16-byte aligned.
+void optim_check_buf(const at::Tensor& t, const char* name, const char* op) {
+  TORCH_CHECK(t.defined(), op, ": ", name, " is undefined");
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be on the GPU");
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ",
+              name, " must be 16-byte aligned");
+}
+
+void optim_check_pg(const at::Tensor& p, const at::Tensor& g, const char* op) {
+  optim_check_buf(p, "p", op);
+  optim_check_buf(g, "g", op);
+  TORCH_CHECK(p.scalar_type() == at::kFloat || p.scalar_type() == at::kBFloat16,
+              op, ": p must be fp32 or bf16");
+  TORCH_CHECK(g.scalar_type() == p.scalar_type(), op, ": g must have p's dtype");
+  TORCH_CHECK(g.device() == p.device(), op, ": g must be on p's device");
+  TORCH_CHECK(g.numel() == p.numel(), op, ": g must have p's ", p.numel(),
+              " elements, got ", g.numel());
+}
+
+// fp32 moment of p's size on p's device
+void optim_check_moment(const at::Tensor& t, const char* name,
+                        const at::Tensor& p, const char* op) {
+  optim_check_buf(t, name, op);
+  TORCH_CHECK(t.device() == p.device(), op, ": ", name,
+              " must be on p's device");
+  TORCH_CHECK(t.scalar_type() == at::kFloat, op, ": ", name, " must be fp32");
+  TORCH_CHECK(t.numel() == p.numel(), op, ": ", name, " must have p's ",
+              p.numel(), " elements, got ", t.numel());
+}
+
+// partials / clip_state: contiguous fp32 on dev
+void optim_check_f32(const at::Tensor& t, const char* name, c10::Device dev,
+                     const char* op) {
+  TORCH_CHECK(t.defined(), op, ": ", name, " is undefined");
+  TORCH_CHECK(t.is_cuda() && t.device() == dev, op, ": ", name,
+              " must be on the gradients' device");
+  TORCH_CHECK(t.scalar_type() == at::kFloat, op, ": ", name, " must be fp32");
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+}
+
+const float* optim_clip_state(const c10::optional<at::Tensor>& cs,
+                              const at::Tensor& p, const char* op) {
+  if (!cs.has_value() || !cs->defined()) return nullptr;
+  optim_check_f32(*cs, "clip_state", p.device(), op);
+  TORCH_CHECK(cs->numel() == 4, op, ": clip_state must have 4 elements, got ",
+              cs->numel());
+  return cs->data_ptr<float>();
+}
+
+}  // namespace
+
+long long optim_grid_py(long long n) {
+  TORCH_CHECK(n >= 0, "optim_grid: n must be >= 0");
+  return optim_grid(n);
+}
+
+long long grad_sumsq(at::Tensor g, at::Tensor partials, long long offset) {
+  const char* op = "grad_sumsq";
+  optim_check_buf(g, "g", op);
+  TORCH_CHECK(g.scalar_type() == at::kFloat || g.scalar_type() == at::kBFloat16,
+              op, ": g must be fp32 or bf16");
+  optim_check_f32(partials, "partials", g.device(), op);
+  const long long nblocks = optim_grid(g.numel());
+  TORCH_CHECK(offset >= 0 && offset + nblocks <= partials.numel(), op,
+              ": offset ", offset, " + ", nblocks, " blocks is beyond partials (",
+              partials.numel(), " elements)");
+  launch_grad_sumsq(is_bf16(g), g.data_ptr(), g.numel(),
+                    partials.data_ptr<float>() + offset, stream());
+  return nblocks;
+}
+
+void clip_finalize(at::Tensor partials, long long count, double max_norm,
+                   at::Tensor clip_state) {
+  const char* op = "clip_finalize";
+  TORCH_CHECK(partials.defined() && partials.is_cuda(), op,
+              ": partials must be on the GPU");
+  optim_check_f32(partials, "partials", partials.device(), op);
+  optim_check_f32(clip_state, "clip_state", partials.device(), op);
+  TORCH_CHECK(clip_state.numel() == 4, op,
+              ": clip_state must have 4 elements, got ", clip_state.numel());
+  TORCH_CHECK(count >= 0 && count <= partials.numel(), op, ": count ", count,
+              " is beyond partials (", partials.numel(), " elements)");
+  TORCH_CHECK(max_norm > 0.0, op, ": max_norm must be > 0 and not NaN, got ",
+              max_norm);
+  launch_clip_finalize(partials.data_ptr<float>(), (int)count, max_norm,
+                       clip_state.data_ptr<float>(), stream());
+}
+
+void sgd_step_ext(at::Tensor p, at::Tensor g, at::Tensor m, double lr,
+                  double momentum, double weight_decay, bool zero_grad,
+                  c10::optional<at::Tensor> clip_state, bool decoupled) {
+  const char* op = "sgd_step_ext";
+  optim_check_pg(p, g, op);
+  float* mptr = nullptr;
+  if (m.defined() && m.numel() > 0) {
+    optim_check_moment(m, "m", p, op);
+    mptr = m.data_ptr<float>();
+  }
+  const float* cs = optim_clip_state(clip_state, p, op);
+  launch_sgd_ext(is_bf16(p), p.data_ptr(), g.data_ptr(), mptr, p.numel(),
+                 (float)lr, (float)momentum, (float)weight_decay,
+                 zero_grad ? 1 : 0, cs, decoupled ? 1 : 0, stream());
+}
+
+void adam_step_ext(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
+                   double lr, double beta1, double beta2, double eps,
+                   double weight_decay, double bc1, double bc2, bool zero_grad,
+                   c10::optional<at::Tensor> clip_state, bool decoupled) {
+  const char* op = "adam_step_ext";
+  optim_check_pg(p, g, op);
+  optim_check_moment(m, "m", p, op);
+  optim_check_moment(v, "v", p, op);
+  const float* cs = optim_clip_state(clip_state, p, op);
+  launch_adam_ext(is_bf16(p), p.data_ptr(), g.data_ptr(), m.data_ptr<float>(),
+                  v.data_ptr<float>(), p.numel(), (float)lr, (float)beta1,
+                  (float)beta2, (float)eps, (float)weight_decay,
+                  (float)(1.0 / bc1), (float)(1.0 / std::sqrt(bc2)),
+                  zero_grad ? 1 : 0, cs, decoupled ? 1 : 0, stream());
+}
+
 // ---- fedmath ---------------------------------------------------------------
 
 void scale_cast(at::Tensor dst, at::Tensor src, double alpha) {
@@ -1343,6 +1469,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("m"), py::arg("v"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
         py::arg("bc1"), py::arg("bc2"), py::arg("zero_grad") = false);
+  m.def("optim_grid", &optim_grid_py, py::arg("n"));
+  m.def("grad_sumsq", &grad_sumsq, py::arg("g"), py::arg("partials"),
+        py::arg("offset"));
+  m.def("clip_finalize", &clip_finalize, py::arg("partials"), py::arg("count"),
+        py::arg("max_norm"), py::arg("clip_state"));
+  m.def("sgd_step_ext", &sgd_step_ext, py::arg("p"), py::arg("g"), py::arg("m"),
+        py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
+        py::arg("zero_grad") = false, py::arg("clip_state") = py::none(),
+        py::arg("decoupled") = false);
+  m.def("adam_step_ext", &adam_step_ext, py::arg("p"), py::arg("g"),
+        py::arg("m"), py::arg("v"), py::arg("lr"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("bc1"), py::arg("bc2"), py::arg("zero_grad") = false,
+        py::arg("clip_state") = py::none(), py::arg("decoupled") = false);
   m.def("scale_cast", &scale_cast);
   m.def("cast_copy", &cast_copy);
   m.def("axpby", &axpby);

@@ -18,6 +18,22 @@ void launch_adam(bool is_bf16, void* p, void* g, float* m, float* v,
                  long long n, float lr, float b1, float b2, float eps, float wd,
                  float inv_bc1, float inv_sqrt_bc2, int zero_after,
                  hipStream_t s);
+// Blocks of the step and sumsq kernels for n elements: what grad_sumsq writes.
+int optim_grid(long long n);
+// The EXT steps: clip_state (may be null) as clip_finalize wrote it.
+void launch_sgd_ext(bool is_bf16, void* p, void* g, float* m, long long n,
+                    float lr, float momentum, float wd, int zero_after,
+                    const float* clip_state, int decoupled, hipStream_t s);
+void launch_adam_ext(bool is_bf16, void* p, void* g, float* m, float* v,
+                     long long n, float lr, float b1, float b2, float eps,
+                     float wd, float inv_bc1, float inv_sqrt_bc2,
+                     int zero_after, const float* clip_state, int decoupled,
+                     hipStream_t s);
+// One fp32 partial per block at partials[0 .. grid); returns the grid.
+int launch_grad_sumsq(bool is_bf16, const void* g, long long n,
+                      float* partials, hipStream_t s);
+void launch_clip_finalize(const float* partials, int count, double max_norm,
+                          float* clip_state, hipStream_t s);
 
 // fedmath.hip
 void launch_scale_cast(bool src_bf16, float* dst, const void* src, long long n,

@@ -48,6 +48,7 @@ def client_main(args) -> None:
         optimizer=args.optimizer,
         momentum=0.9 if args.optimizer == "sgd" else 0.0,
         fedprox_mu=args.fedprox_mu,
+        max_grad_norm=args.max_grad_norm,
     )
     cfg.control.heartbeat_interval = 5.0
 
@@ -164,7 +165,10 @@ def main() -> None:
     p.add_argument("--batch-size", type=int, default=256)
     p.add_argument("--seq-len", type=int, default=128)
     p.add_argument("--lr", type=float, default=0.05)
-    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adam"])
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adam", "adamw"])
+    p.add_argument("--max-grad-norm", type=float, default=0.0,
+                   help="clip the global gradient norm and skip non-finite "
+                        "steps; 0 = off")
     p.add_argument("--fedprox-mu", type=float, default=0.0)
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--port", type=int, default=8080)

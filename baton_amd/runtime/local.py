@@ -37,6 +37,11 @@ class LocalTrainer:
     it: ``data = (ids, seq_lens, labels)`` calls ``model(ids, seq_lens)``
     (right-padded batches, models/bert.py). The captured per-minibatch graph
     step takes a single input, so data with more than one input runs eagerly.
+
+    ``config.max_grad_norm > 0`` clips inside ``opt.step()`` (ops/optim.py):
+    the global norm is taken over the gradients as the step finds them. The
+    FedProx term is added to them before ``opt.step()``, so the clipped norm
+    includes it; a step with a non-finite gradient is skipped on the device.
     """
 
     def __init__(

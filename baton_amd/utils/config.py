@@ -49,9 +49,11 @@ class TrainConfig:
     n_epoch: int = 32                # reference manager.py:55 default round length
     lr: float = 1e-3                 # reference demo.py:29
     batch_size: int = 32             # reference demo.py:29
-    optimizer: str = "sgd"           # 'sgd' | 'adam'
+    optimizer: str = "sgd"           # 'sgd' | 'adam' | 'adamw' (decoupled decay)
     momentum: float = 0.0
     weight_decay: float = 0.0
+    max_grad_norm: float = 0.0       # >0 clips the global grad norm and skips
+                                     # non-finite steps; 0 = off
     adam_betas: tuple = (0.9, 0.999)
     adam_eps: float = 1e-8
     fedprox_mu: float = 0.0          # >0 enables FedProx proximal term

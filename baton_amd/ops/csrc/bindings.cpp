@@ -111,30 +111,60 @@ NormShape norm_shape(const at::Tensor& x, const char* op, bool rows_fit_int) {
   return {R, (int)C};
 }
 
-// dy / res / plus / y_post: x's sizes, dtype and device, contiguous.
-void norm_check_like_x(const at::Tensor& t, const char* name,
-                       const at::Tensor& x, const char* op) {
+// A second tensor that must match the first one (xs names it as a possessive,
+// "x's"): its device, dtype and contiguity, and its sizes (flat: its element
+// count, for the streaming ops).
+void check_like(const at::Tensor& t, const char* name, const at::Tensor& x,
+                const char* xs, const char* op, bool flat = false) {
   TORCH_CHECK(t.defined(), op, ": ", name, " is undefined");
   TORCH_CHECK(t.is_cuda() && t.device() == x.device(), op, ": ", name,
-              " must be on x's device");
+              " must be on ", xs, " device");
   TORCH_CHECK(t.scalar_type() == x.scalar_type(), op, ": ", name,
-              " must have x's dtype");
-  TORCH_CHECK(t.sizes() == x.sizes(), op, ": ", name, " must have x's sizes ",
-              x.sizes(), ", got ", t.sizes());
+              " must have ", xs, " dtype");
+  if (flat) {
+    TORCH_CHECK(t.numel() == x.numel(), op, ": ", name, " must have ", xs, " ",
+                x.numel(), " elements, got ", t.numel());
+  } else {
+    TORCH_CHECK(t.sizes() == x.sizes(), op, ": ", name, " must have ", xs,
+                " sizes ", x.sizes(), ", got ", t.sizes());
+  }
   TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
 }
 
-// A contiguous vector of exactly n elements of dtype dt on x's device: w / b
-// (x's dtype), mean / rstd / gamma / beta / running statistics (fp32).
-void norm_check_vec(const at::Tensor& t, const char* name, const at::Tensor& x,
-                    at::ScalarType dt, long long n, const char* op) {
+// A contiguous buffer of exactly n elements of dtype dt on the device of x.
+void check_vec(const at::Tensor& t, const char* name, const at::Tensor& x,
+               const char* xs, at::ScalarType dt, long long n,
+               const char* op) {
   TORCH_CHECK(t.defined(), op, ": ", name, " is undefined");
   TORCH_CHECK(t.is_cuda() && t.device() == x.device(), op, ": ", name,
-              " must be on x's device");
+              " must be on ", xs, " device");
   TORCH_CHECK(t.scalar_type() == dt, op, ": ", name, " must be ",
-              dt == at::kFloat ? "fp32" : "of x's dtype");
+              dt == at::kFloat  ? "fp32"
+              : dt == at::kLong ? "int64"
+                                : "of x's dtype");
   TORCH_CHECK(t.numel() == n, op, ": ", name, " must have ", n,
               " elements, got ", t.numel());
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+}
+
+// dy / res / plus / y_post: x's sizes, dtype and device, contiguous.
+void norm_check_like_x(const at::Tensor& t, const char* name,
+                       const at::Tensor& x, const char* op) {
+  check_like(t, name, x, "x's", op);
+}
+
+// w / b (x's dtype), mean / rstd / gamma / beta / running statistics (fp32).
+void norm_check_vec(const at::Tensor& t, const char* name, const at::Tensor& x,
+                    at::ScalarType dt, long long n, const char* op) {
+  check_vec(t, name, x, "x's", dt, n, op);
+}
+
+// The first tensor of a streaming op: fp32 / bf16, contiguous, on the GPU.
+void check_first(const at::Tensor& t, const char* name, const char* op) {
+  TORCH_CHECK(t.defined(), op, ": ", name, " is undefined");
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be on the GPU");
+  TORCH_CHECK(t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16,
+              op, ": ", name, " must be fp32 or bf16");
   TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
 }
 
@@ -305,44 +335,67 @@ void adam_step_ext(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
 // ---- fedmath ---------------------------------------------------------------
 
 void scale_cast(at::Tensor dst, at::Tensor src, double alpha) {
-  TORCH_CHECK(dst.scalar_type() == at::kFloat && dst.is_contiguous());
-  check_compute(src, "src");
-  TORCH_CHECK(dst.numel() == src.numel());
+  const char* op = "scale_cast";
+  check_first(src, "src", op);
+  check_vec(dst, "dst", src, "src's", at::kFloat, src.numel(), op);
   launch_scale_cast(is_bf16(src), dst.data_ptr<float>(), src.data_ptr(),
                     src.numel(), (float)alpha, stream());
 }
 
 void cast_copy(at::Tensor dst, at::Tensor src) {
-  check_compute(dst, "dst");
-  TORCH_CHECK(src.scalar_type() == at::kFloat && src.is_contiguous());
-  TORCH_CHECK(dst.numel() == src.numel());
+  const char* op = "cast_copy";
+  check_first(dst, "dst", op);
+  check_vec(src, "src", dst, "dst's", at::kFloat, dst.numel(), op);
   launch_cast_copy(is_bf16(dst), dst.data_ptr(), src.data_ptr<float>(),
                    dst.numel(), stream());
 }
 
 at::Tensor colsum(at::Tensor x) {
-  check_compute(x, "x");
-  int C = x.size(-1);
-  long long R = x.numel() / C;
-  auto out = at::zeros({C}, x.options().dtype(at::kFloat));
-  launch_colsum(is_bf16(x), x.data_ptr(), out.data_ptr<float>(), R, C,
+  check_first(x, "x", "colsum");
+  const NormShape sh = norm_shape(x, "colsum", false);
+  auto out = at::zeros({sh.C}, x.options().dtype(at::kFloat));
+  launch_colsum(is_bf16(x), x.data_ptr(), out.data_ptr<float>(), sh.R, sh.C,
                 stream());
   return out;
 }
 
+// [R, C] -> [C, R] through the LDS tile kernel the GEMM router uses.
+at::Tensor transpose2d(at::Tensor x) {
+  const char* op = "transpose2d";
+  check_first(x, "x", op);
+  TORCH_CHECK(x.dim() == 2, op, ": x must be 2-D [R, C], got ", x.dim(), "-D");
+  const long long R = x.size(0), C = x.size(1);
+  TORCH_CHECK(R <= INT_MAX && C <= INT_MAX, op, ": x [", R, ", ", C,
+              "] is past the kernel's int");
+  auto out = at::empty({C, R}, x.options());
+  if (x.numel() > 0)
+    launch_transpose(is_bf16(x), x.data_ptr(), out.data_ptr(), (int)R, (int)C,
+                     stream());
+  return out;
+}
+
 void axpby(at::Tensor y, at::Tensor x, double a, double b) {
-  TORCH_CHECK(y.scalar_type() == at::kFloat && x.scalar_type() == at::kFloat);
-  TORCH_CHECK(y.numel() == x.numel());
+  const char* op = "axpby";
+  TORCH_CHECK(y.defined() && y.is_cuda(), op, ": y must be on the GPU");
+  TORCH_CHECK(y.scalar_type() == at::kFloat, op, ": y must be fp32");
+  TORCH_CHECK(y.is_contiguous(), op, ": y must be contiguous");
+  check_vec(x, "x", y, "y's", at::kFloat, y.numel(), op);
   launch_axpby(y.data_ptr<float>(), x.data_ptr<float>(), y.numel(), (float)a,
                (float)b, stream());
 }
 
 // ---- loss ------------------------------------------------------------------
 
+// dout of a scalar loss: one fp32 element on x's device.
+static void check_dout(const at::Tensor& dout, const at::Tensor& x,
+                       const char* xs, const char* op) {
+  check_vec(dout, "dout", x, xs, at::kFloat, 1, op);
+}
+
 at::Tensor mse_fwd(at::Tensor x, at::Tensor y) {
-  check_compute(x, "x");
-  check_compute(y, "y");
-  TORCH_CHECK(x.numel() == y.numel());
+  const char* op = "mse_fwd";
+  check_first(x, "x", op);
+  check_like(y, "y", x, "x's", op, true);
   auto out = at::zeros({}, x.options().dtype(at::kFloat));
   launch_mse_fwd(is_bf16(x), x.data_ptr(), y.data_ptr(), out.data_ptr<float>(),
                  x.numel(), stream());
@@ -351,21 +404,32 @@ at::Tensor mse_fwd(at::Tensor x, at::Tensor y) {
 }
 
 at::Tensor mse_bwd(at::Tensor x, at::Tensor y, at::Tensor dout) {
-  check_compute(x, "x");
-  check_compute(y, "y");
-  TORCH_CHECK(dout.scalar_type() == at::kFloat);
+  const char* op = "mse_bwd";
+  check_first(x, "x", op);
+  check_like(y, "y", x, "x's", op, true);
+  check_dout(dout, x, "x's", op);
   auto dx = at::empty_like(x);
   launch_mse_bwd(is_bf16(x), x.data_ptr(), y.data_ptr(), dout.data_ptr<float>(),
                  dx.data_ptr(), x.numel(), stream());
   return dx;
 }
 
+// logits [B, C] and the int64 labels, as ce_fwd takes them.
+static void check_ce(const char* op, const at::Tensor& logits,
+                     const at::Tensor& target) {
+  check_first(logits, "logits", op);
+  TORCH_CHECK(logits.dim() == 2, op, ": logits must be 2-D [B, C], got ",
+              logits.dim(), "-D");
+  TORCH_CHECK(logits.size(0) <= INT_MAX && logits.size(1) <= INT_MAX, op,
+              ": logits [", logits.size(0), ", ", logits.size(1),
+              "] is past the kernels' int");
+  check_vec(target, "target", logits, "the logits'", at::kLong,
+            logits.size(0), op);
+}
+
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target) {
-  check_compute(logits, "logits");
-  TORCH_CHECK(logits.dim() == 2);
-  TORCH_CHECK(target.scalar_type() == at::kLong && target.is_contiguous());
+  check_ce("ce_fwd", logits, target);
   int B = logits.size(0), C = logits.size(1);
-  TORCH_CHECK(target.numel() == B);
   auto lse = at::empty({B}, logits.options().dtype(at::kFloat));
   auto loss = at::zeros({}, logits.options().dtype(at::kFloat));
   launch_ce_fwd(is_bf16(logits), logits.data_ptr(), reinterpret_cast<const long long*>(target.data_ptr<int64_t>()),
@@ -376,7 +440,11 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target) {
 
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor lse,
                   at::Tensor dout) {
-  check_compute(logits, "logits");
+  const char* op = "ce_bwd";
+  check_ce(op, logits, target);
+  check_vec(lse, "lse", logits, "the logits'", at::kFloat, logits.size(0),
+            op);
+  check_dout(dout, logits, "the logits'", op);
   int B = logits.size(0), C = logits.size(1);
   auto dx = at::empty_like(logits);
   launch_ce_bwd(is_bf16(logits), logits.data_ptr(), reinterpret_cast<const long long*>(target.data_ptr<int64_t>()),
@@ -658,14 +726,15 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor y_post,
 // ---- elementwise -----------------------------------------------------------
 
 at::Tensor relu_fwd(at::Tensor x) {
-  check_compute(x, "x");
+  check_first(x, "x", "relu_fwd");
   auto y = at::empty_like(x);
   launch_relu_fwd(is_bf16(x), x.data_ptr(), y.data_ptr(), x.numel(), stream());
   return y;
 }
 
 at::Tensor relu_bwd(at::Tensor dy, at::Tensor y) {
-  check_compute(dy, "dy");
+  check_first(dy, "dy", "relu_bwd");
+  check_like(y, "y", dy, "dy's", "relu_bwd", true);
   auto dx = at::empty_like(dy);
   launch_relu_bwd(is_bf16(dy), dy.data_ptr(), y.data_ptr(), dx.data_ptr(),
                   dy.numel(), stream());
@@ -673,9 +742,8 @@ at::Tensor relu_bwd(at::Tensor dy, at::Tensor y) {
 }
 
 at::Tensor add_relu_fwd(at::Tensor a, at::Tensor b) {
-  check_compute(a, "a");
-  check_compute(b, "b");
-  TORCH_CHECK(a.numel() == b.numel());
+  check_first(a, "a", "add_relu_fwd");
+  check_like(b, "b", a, "a's", "add_relu_fwd", true);
   auto y = at::empty_like(a);
   launch_add_relu_fwd(is_bf16(a), a.data_ptr(), b.data_ptr(), y.data_ptr(),
                       a.numel(), stream());
@@ -683,9 +751,8 @@ at::Tensor add_relu_fwd(at::Tensor a, at::Tensor b) {
 }
 
 at::Tensor add_scaled_fwd(at::Tensor a, at::Tensor b, double alpha) {
-  check_compute(a, "a");
-  check_compute(b, "b");
-  TORCH_CHECK(a.numel() == b.numel());
+  check_first(a, "a", "add_scaled_fwd");
+  check_like(b, "b", a, "a's", "add_scaled_fwd", true);
   auto z = at::empty_like(a);
   launch_add_scaled_fwd(is_bf16(a), a.data_ptr(), b.data_ptr(), z.data_ptr(),
                         (float)alpha, a.numel(), stream());
@@ -693,7 +760,7 @@ at::Tensor add_scaled_fwd(at::Tensor a, at::Tensor b, double alpha) {
 }
 
 at::Tensor scale_fwd(at::Tensor x, double alpha) {
-  check_compute(x, "x");
+  check_first(x, "x", "scale_fwd");
   auto z = at::empty_like(x);
   launch_scale_fwd(is_bf16(x), x.data_ptr(), z.data_ptr(), (float)alpha,
                    x.numel(), stream());
@@ -701,14 +768,15 @@ at::Tensor scale_fwd(at::Tensor x, double alpha) {
 }
 
 at::Tensor gelu_fwd(at::Tensor x) {
-  check_compute(x, "x");
+  check_first(x, "x", "gelu_fwd");
   auto y = at::empty_like(x);
   launch_gelu_fwd(is_bf16(x), x.data_ptr(), y.data_ptr(), x.numel(), stream());
   return y;
 }
 
 at::Tensor gelu_bwd(at::Tensor dy, at::Tensor x) {
-  check_compute(dy, "dy");
+  check_first(dy, "dy", "gelu_bwd");
+  check_like(x, "x", dy, "dy's", "gelu_bwd", true);
   auto dx = at::empty_like(dy);
   launch_gelu_bwd(is_bf16(dy), dy.data_ptr(), x.data_ptr(), dx.data_ptr(),
                   dy.numel(), stream());
@@ -1259,25 +1327,49 @@ at::Tensor softmax_bwd(at::Tensor y, at::Tensor dy, double scale) {
 
 // ---- llama ops -------------------------------------------------------------
 
+// cos_t / sin_t: contiguous fp32 [rows >= S, D / 2] on x's device.
+static void check_rope_table(const at::Tensor& t, const char* name,
+                             const at::Tensor& x, long long S, long long half) {
+  const char* op = "rope";
+  TORCH_CHECK(t.defined(), op, ": ", name, " is undefined");
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device(), op, ": ", name,
+              " must be on x's device");
+  TORCH_CHECK(t.scalar_type() == at::kFloat, op, ": ", name, " must be fp32");
+  TORCH_CHECK(t.dim() == 2, op, ": ", name, " must be 2-D [rows, D / 2], got ",
+              t.dim(), "-D");
+  TORCH_CHECK(t.size(0) >= S && t.size(1) == half, op, ": ", name,
+              " must have at least S = ", S, " rows and exactly D / 2 = ", half,
+              " columns, got ", t.sizes());
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+}
+
 at::Tensor rope(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t,
                 bool inverse) {
-  check_compute(x, "x");
-  TORCH_CHECK(x.dim() == 4, "rope wants [B,S,H,D]");
-  TORCH_CHECK(cos_t.scalar_type() == at::kFloat && sin_t.scalar_type() == at::kFloat);
-  int S = x.size(1), H = x.size(2), D = x.size(3);
-  TORCH_CHECK(cos_t.size(0) >= S && cos_t.size(1) == D / 2, "rope table shape");
+  const char* op = "rope";
+  check_first(x, "x", op);
+  TORCH_CHECK(x.dim() == 4, op, ": x must be 4-D [B, S, H, D], got ", x.dim(),
+              "-D");
+  const long long S = x.size(1), H = x.size(2), D = x.size(3);
+  TORCH_CHECK(D > 0 && D % 2 == 0, op, ": x must have an even D > 0, got ", D);
+  TORCH_CHECK(S <= INT_MAX && H <= INT_MAX && D <= INT_MAX, op,
+              ": x has S, H or D past the kernel's int");
+  check_rope_table(cos_t, "cos_t", x, S, D / 2);
+  check_rope_table(sin_t, "sin_t", x, S, D / 2);
+  TORCH_CHECK(sin_t.sizes() == cos_t.sizes(), op,
+              ": sin_t must have cos_t's sizes ", cos_t.sizes(), ", got ",
+              sin_t.sizes());
   auto y = at::empty_like(x);
   long long total = x.numel() / 2;
-  launch_rope(is_bf16(x), inverse, x.data_ptr(), y.data_ptr(),
-              cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), total, S, H, D,
-              stream());
+  if (total > 0)
+    launch_rope(is_bf16(x), inverse, x.data_ptr(), y.data_ptr(),
+                cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), total, (int)S,
+                (int)H, (int)D, stream());
   return y;
 }
 
 at::Tensor silu_mul_fwd(at::Tensor a, at::Tensor b) {
-  check_compute(a, "a");
-  check_compute(b, "b");
-  TORCH_CHECK(a.numel() == b.numel());
+  check_first(a, "a", "silu_mul_fwd");
+  check_like(b, "b", a, "a's", "silu_mul_fwd", true);
   auto y = at::empty_like(a);
   launch_silu_mul_fwd(is_bf16(a), a.data_ptr(), b.data_ptr(), y.data_ptr(),
                       a.numel(), stream());
@@ -1285,7 +1377,9 @@ at::Tensor silu_mul_fwd(at::Tensor a, at::Tensor b) {
 }
 
 std::vector<at::Tensor> silu_mul_bwd(at::Tensor dy, at::Tensor a, at::Tensor b) {
-  check_compute(dy, "dy");
+  check_first(dy, "dy", "silu_mul_bwd");
+  check_like(a, "a", dy, "dy's", "silu_mul_bwd", true);
+  check_like(b, "b", dy, "dy's", "silu_mul_bwd", true);
   auto da = at::empty_like(a);
   auto db = at::empty_like(b);
   launch_silu_mul_bwd(is_bf16(a), dy.data_ptr(), a.data_ptr(), b.data_ptr(),
@@ -1495,6 +1589,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sbO") = 0, py::arg("sbI") = 0, py::arg("ldb") = 0,
         py::arg("scO") = 0, py::arg("scI") = 0, py::arg("ldc") = 0);
   m.def("colsum", &colsum);
+  m.def("transpose2d", &transpose2d);
   m.def("mse_fwd", &mse_fwd);
   m.def("mse_bwd", &mse_bwd);
   m.def("ce_fwd", &ce_fwd);

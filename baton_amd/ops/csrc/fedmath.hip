@@ -33,6 +33,25 @@ __global__ void scale_cast_kernel(float* __restrict__ dst,
     dst[i] = alpha * (float)src[i];
 }
 
+// f32 -> 16-B vector for cast_copy's body. bf16 rounds to nearest even as
+// VecTraits<bf16>::from_float does, but a NaN stays a NaN: there the rounding
+// add carries a payload of all ones into the exponent and sign (0x7fffffff ->
+// -0.0, 0xffffffff -> +0.0) and rounds a low payload away (0x7f800001 ->
+// +inf). This op installs the all-reduce buffer, which holds what other
+// clients sent, so it cannot assume hardware-made NaNs (0x7fc00000).
+DEVINL void cast_from_float(const float* in, f32x4& v) {
+  VecTraits<float>::from_float(in, v);
+}
+DEVINL void cast_from_float(const float* in, s16x8& v) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const unsigned int u = __float_as_uint(in[i]);
+    const unsigned int rounded = u + 0x7fff + ((u >> 16) & 1);
+    const bool nan = (u & 0x7fffffffu) > 0x7f800000u;
+    v[i] = (short)(nan ? ((u >> 16) | 0x0040u) : (rounded >> 16));
+  }
+}
+
 // dst(T) = src(f32)
 template <typename T>
 __global__ void cast_copy_kernel(T* __restrict__ dst,
@@ -50,7 +69,7 @@ __global__ void cast_copy_kernel(T* __restrict__ dst,
       for (int k = 0; k < 4; ++k) f[q * 4 + k] = s[k];
     }
     typename VT::VecT o;
-    VT::from_float(f, o);
+    cast_from_float(f, o);
     reinterpret_cast<typename VT::VecT*>(dst)[i] = o;
   }
   for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -406,7 +406,7 @@ class ReLUFn(torch.autograd.Function):
         dy = dy.contiguous()
         if _on_gpu(dy):
             return require_hip().relu_bwd(dy, y)
-        return dy * (y > 0).to(dy.dtype)
+        return torch.where(y > 0, dy, torch.zeros_like(dy))  # selects, as the kernel
 
 
 def relu(x):
@@ -433,7 +433,7 @@ class AddReLUFn(torch.autograd.Function):
         if _on_gpu(dy):
             da = require_hip().relu_bwd(dy, y)
         else:
-            da = dy * (y > 0).to(dy.dtype)
+            da = torch.where(y > 0, dy, torch.zeros_like(dy))
         return da, da
 
 
@@ -451,7 +451,10 @@ class AddScaledFn(torch.autograd.Function):
         ctx.alpha = alpha
         if _on_gpu(a):
             return require_hip().add_scaled_fwd(a, b, alpha)
-        return a + alpha * b
+        # one rounding, as the kernel's fma: float32(alpha) * b is exact in
+        # float64 (bf16 would round the product before the add)
+        al = torch.tensor(alpha, dtype=torch.float32).double()
+        return (a.double() + al * b.double()).to(a.dtype)
 
     @staticmethod
     def backward(ctx, dz):

@@ -15,6 +15,11 @@ Fixed-by-design relative to the reference:
   D8  experiment name is explicit or a deterministic digest of the model
       architecture (never Python object hash).
 
+Server optimizer: with ``config.server_opt.name`` other than 'none', the
+'fedavg' mode aggregates through fed.server_opt.ServerOptimizer (clipped
+client updates, FedAvgM / FedAdagrad / FedAdam / FedYogi on an fp32 master);
+its state is a sidecar ``<name>.server_opt.ckpt`` beside the checkpoint.
+
 Checkpoint/resume: the global model is persisted per round
 with the round-start payload schema {'state_dict', 'update_name', 'n_epoch'}
 — the wire format IS the checkpoint layout, as in the reference.
@@ -36,6 +41,7 @@ from baton_amd.control.registry import ClientRegistry
 from baton_amd.control.rounds import RoundInProgress, RoundState
 from baton_amd.control.wire import decode_payload, encode_payload
 from baton_amd.fed.aggregate import fedavg_, weighted_loss_history
+from baton_amd.fed.server_opt import ServerOptimizer
 from baton_amd.utils.config import BatonConfig
 from baton_amd.utils.json_clean import json_clean
 
@@ -75,6 +81,11 @@ class Experiment:
             "total_samples": 0,
             "last_round_sec": 0.0,
         }
+        # None with server_opt.name == 'none': end_round then runs fedavg_
+        self.server_opt = ServerOptimizer.from_config(self.config.server_opt)
+        if self.server_opt is not None:
+            self.metrics["skipped_rounds"] = 0
+            self.metrics["last_round_W"] = 0.0
         if app is not None:
             self.register_handlers(app)
 
@@ -272,7 +283,15 @@ class Experiment:
                     "aggregation_mode is 'fedavg'"
                 )
             sds = [r["state_dict"] for r in responses.values()]
-            fedavg_(self.model.state_dict(), sds, weights)
+            if self.server_opt is None:
+                fedavg_(self.model.state_dict(), sds, weights)
+            else:
+                self.server_opt.step_(
+                    self.model.state_dict(), sds, weights,
+                    [n for n, _ in self.model.named_parameters()],
+                )
+                self.metrics["skipped_rounds"] = self.server_opt.skipped_rounds
+                self.metrics["last_round_W"] = self.server_opt.last_W
             self.rounds.loss_history.extend(
                 weighted_loss_history(
                     [r["loss_history"] for r in responses.values()], weights
@@ -316,6 +335,49 @@ class Experiment:
         with open(tmp, "wb") as f:
             f.write(payload)
         os.replace(tmp, path)
+        self._save_server_opt()
+
+    def _server_opt_path(self) -> Optional[str]:
+        """The server optimizer's sidecar, in the wire format, beside the
+        checkpoint (whose own contents stay the round-start payload)."""
+        d = self.config.checkpoint_dir
+        if not d:
+            return None
+        return os.path.join(d, f"{self.name}.server_opt.ckpt")
+
+    def _save_server_opt(self) -> None:
+        path = self._server_opt_path()
+        if path is None or self.server_opt is None:
+            return
+        payload = encode_payload(
+            {
+                "server_opt": self.server_opt.name,
+                "round_index": self.rounds.round_index,
+                "last_round_W": self.server_opt.last_W,
+            },
+            self.server_opt.state_dict(),
+        )
+        tmp = path + ".tmp"
+        with open(tmp, "wb") as f:
+            f.write(payload)
+        os.replace(tmp, path)
+
+    def _load_server_opt(self) -> bool:
+        path = self._server_opt_path()
+        if path is None or self.server_opt is None or not os.path.exists(path):
+            return False
+        with open(path, "rb") as f:
+            meta, tensors = decode_payload(f.read())
+        if meta.get("server_opt") != self.server_opt.name:
+            raise ValueError(
+                f"{path} holds the state of server optimizer "
+                f"{meta.get('server_opt')!r}, not {self.server_opt.name!r}"
+            )
+        self.server_opt.load_state_dict(tensors)
+        self.server_opt.last_W = float(meta.get("last_round_W", 0.0))
+        self.metrics["skipped_rounds"] = self.server_opt.skipped_rounds
+        self.metrics["last_round_W"] = self.server_opt.last_W
+        return True
 
     def load_checkpoint(self) -> bool:
         """Resume the global model + round counter from disk. Returns True
@@ -328,6 +390,7 @@ class Experiment:
         self.model.load_state_dict(tensors)
         self.rounds.round_index = int(meta.get("round_index", 0))
         self.rounds.loss_history = list(meta.get("loss_history", []))
+        self._load_server_opt()
         log.info("resumed %s at round %d", self.name, self.rounds.round_index)
         return True
 

@@ -350,6 +350,130 @@ void cast_copy(at::Tensor dst, at::Tensor src) {
                    dst.numel(), stream());
 }
 
+// ---- fedopt (the federated server step) --------------------------------------
+// Everything these ops refuse is refused here, before any launch, by argument
+// name.
+
+namespace {
+
+// A buffer of a fedopt op: on the GPU (dev when given), contiguous, 16-byte
+// aligned; fp32 unless any_float, n elements unless n < 0.
+void fedopt_check(const at::Tensor& t, const char* name, const char* op,
+                  const c10::optional<c10::Device>& dev = c10::nullopt,
+                  long long n = -1, bool any_float = false) {
+  TORCH_CHECK(t.defined(), op, ": ", name, " is undefined");
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be on the GPU");
+  TORCH_CHECK(!dev.has_value() || t.device() == *dev, op, ": ", name,
+              " must be on the device of the other tensors");
+  if (any_float) {
+    TORCH_CHECK(
+        t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16, op,
+        ": ", name, " must be fp32 or bf16");
+  } else {
+    TORCH_CHECK(t.scalar_type() == at::kFloat, op, ": ", name,
+                " must be fp32");
+  }
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ",
+              name, " must be 16-byte aligned");
+  TORCH_CHECK(n < 0 || t.numel() == n, op, ": ", name, " must have ", n,
+              " elements, got ", t.numel());
+}
+
+int server_mode(const std::string& mode) {
+  static const char* names[] = {"mean", "fedavgm", "fedadagrad", "fedadam",
+                                "fedyogi"};
+  for (int i = 0; i < 5; ++i)
+    if (mode == names[i]) return i;
+  TORCH_CHECK(false, "server_step: unknown mode '", mode,
+              "' (mean, fedavgm, fedadagrad, fedadam, fedyogi)");
+  return -1;
+}
+
+}  // namespace
+
+long long delta_sumsq(at::Tensor theta, at::Tensor x, at::Tensor partials,
+                      long long offset) {
+  const char* op = "delta_sumsq";
+  fedopt_check(theta, "theta", op, c10::nullopt, -1, true);
+  fedopt_check(x, "x", op, theta.device(), theta.numel());
+  fedopt_check(partials, "partials", op, theta.device());
+  const long long nblocks = optim_grid(theta.numel());
+  TORCH_CHECK(offset >= 0 && offset + nblocks <= partials.numel(), op,
+              ": offset ", offset, " + ", nblocks, " blocks is beyond partials (",
+              partials.numel(), " elements)");
+  launch_delta_sumsq(is_bf16(theta), theta.data_ptr(), x.data_ptr<float>(),
+                     theta.numel(), partials.data_ptr<float>() + offset,
+                     stream());
+  return nblocks;
+}
+
+void delta_scale_cast(at::Tensor dst, at::Tensor theta, at::Tensor x,
+                      double alpha, at::Tensor clip_state,
+                      c10::optional<at::Tensor> w_out) {
+  const char* op = "delta_scale_cast";
+  fedopt_check(theta, "theta", op, c10::nullopt, -1, true);
+  fedopt_check(dst, "dst", op, theta.device(), theta.numel());
+  fedopt_check(x, "x", op, theta.device(), theta.numel());
+  fedopt_check(clip_state, "clip_state", op, theta.device(), 4);
+  float* w = nullptr;
+  if (w_out.has_value() && w_out->defined()) {
+    fedopt_check(*w_out, "w_out", op, theta.device());
+    TORCH_CHECK(w_out->numel() >= 1, op, ": w_out must have an element");
+    w = w_out->data_ptr<float>();
+  }
+  TORCH_CHECK(alpha == alpha, op, ": alpha must not be NaN");
+  launch_delta_scale_cast(is_bf16(theta), dst.data_ptr<float>(),
+                          theta.data_ptr(), x.data_ptr<float>(), theta.numel(),
+                          (float)alpha, clip_state.data_ptr<float>(), w,
+                          stream());
+}
+
+void fedopt_finalize(at::Tensor w_sum, at::Tensor round_state) {
+  const char* op = "fedopt_finalize";
+  fedopt_check(w_sum, "w_sum", op);
+  TORCH_CHECK(w_sum.numel() >= 1, op, ": w_sum must have an element");
+  fedopt_check(round_state, "round_state", op, w_sum.device(), 4);
+  launch_fedopt_finalize(w_sum.data_ptr<float>(),
+                         round_state.data_ptr<float>(), stream());
+}
+
+void server_step(const std::string& mode, at::Tensor D, at::Tensor x,
+                 c10::optional<at::Tensor> m, c10::optional<at::Tensor> v,
+                 double lr, double beta1, double beta2, double tau,
+                 at::Tensor round_state) {
+  const char* op = "server_step";
+  const int md = server_mode(mode);
+  const bool has_m = md >= 1, has_v = md >= 2;
+  fedopt_check(x, "x", op);
+  fedopt_check(D, "D", op, x.device(), x.numel());
+  float *mp = nullptr, *vp = nullptr;
+  if (has_m) {
+    TORCH_CHECK(m.has_value(), op, ": m is undefined (mode ", mode,
+                " keeps a first moment)");
+    fedopt_check(*m, "m", op, x.device(), x.numel());
+    mp = m->data_ptr<float>();
+  }
+  if (has_v) {
+    TORCH_CHECK(v.has_value(), op, ": v is undefined (mode ", mode,
+                " keeps a second moment)");
+    fedopt_check(*v, "v", op, x.device(), x.numel());
+    vp = v->data_ptr<float>();
+  }
+  fedopt_check(round_state, "round_state", op, x.device(), 4);
+  TORCH_CHECK(lr > 0.0, op, ": lr must be > 0 and not NaN, got ", lr);
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0, op,
+              ": beta1 must be in [0, 1) and not NaN, got ", beta1);
+  TORCH_CHECK(beta2 >= 0.0 && beta2 < 1.0, op,
+              ": beta2 must be in [0, 1) and not NaN, got ", beta2);
+  TORCH_CHECK(tau == tau, op, ": tau must not be NaN");
+  TORCH_CHECK(!has_v || tau > 0.0, op,
+              ": tau must be > 0 for an adaptive mode, got ", tau);
+  launch_server_step(md, D.data_ptr<float>(), x.data_ptr<float>(), mp, vp,
+                     x.numel(), (float)lr, (float)beta1, (float)beta2,
+                     (float)tau, round_state.data_ptr<float>(), stream());
+}
+
 at::Tensor colsum(at::Tensor x) {
   check_first(x, "x", "colsum");
   const NormShape sh = norm_shape(x, "colsum", false);
@@ -1577,6 +1701,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
         py::arg("bc1"), py::arg("bc2"), py::arg("zero_grad") = false,
         py::arg("clip_state") = py::none(), py::arg("decoupled") = false);
+  m.def("delta_sumsq", &delta_sumsq, py::arg("theta"), py::arg("x"),
+        py::arg("partials"), py::arg("offset"));
+  m.def("delta_scale_cast", &delta_scale_cast, py::arg("dst"),
+        py::arg("theta"), py::arg("x"), py::arg("alpha"),
+        py::arg("clip_state"), py::arg("w_out") = py::none());
+  m.def("fedopt_finalize", &fedopt_finalize, py::arg("w_sum"),
+        py::arg("round_state"));
+  m.def("server_step", &server_step, py::arg("mode"), py::arg("D"),
+        py::arg("x"), py::arg("m"), py::arg("v"), py::arg("lr"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("tau"),
+        py::arg("round_state"));
   m.def("scale_cast", &scale_cast);
   m.def("cast_copy", &cast_copy);
   m.def("axpby", &axpby);

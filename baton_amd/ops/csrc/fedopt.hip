@@ -1,0 +1,252 @@
+// Federated server step (gfx950): clipped client updates and the server
+// optimizers of Reddi et al., "Adaptive Federated Optimization".
+//
+// Per round, with x the fp32 global model and theta a client's model in its
+// own dtype, every client forms d = float(theta) - x, measures ||d||
+// (delta_sumsq_kernel, then optim.hip's clip_finalize_kernel), and sends
+// alpha * coef * d into the fp32 reduce buffer (delta_scale_cast_kernel); a
+// client whose norm is not finite sends +0.0 and weight 0. The root turns the
+// reduced weight W into round_state (fedopt_finalize_kernel) and applies
+// Delta = D / W to x, m and v (server_step_kernel). All state is fp32, all
+// kernels use the optim.hip geometry (optim_grid blocks of 256 threads, 16 B
+// per lane, scalar tail, grid-stride), and nothing is read back by the host.
+#include "common.h"
+
+// Every operation below is rounded on its own: no a * b + c written with
+// operators may become an fma (the fmas are spelled fmaf).
+#pragma clang fp contract(off)
+
+// ---- client side -----------------------------------------------------------
+
+// grad_sumsq_kernel on float(theta) - x: every thread chains fma(d, d, acc)
+// over the vectors of its grid stride in order, then at most one tail
+// element; one partial per block at partials[blockIdx.x], no atomics.
+template <typename T>
+__global__ void delta_sumsq_kernel(const T* __restrict__ theta,
+                                   const float* __restrict__ x, long long n,
+                                   float* __restrict__ partials) {
+  using VT = VecTraits<T>;
+  constexpr int V = VT::kElems;
+  __shared__ float scratch[kBlock / kWave];
+  const long long nvec = n / V;
+  float acc = 0.f;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
+       i += (long long)gridDim.x * blockDim.x) {
+    float tf[V];
+    VT::to_float(reinterpret_cast<const typename VT::VecT*>(theta)[i], tf);
+#pragma unroll
+    for (int q = 0; q < V / 4; ++q) {
+      const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i * (V / 4) + q];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float d = tf[q * 4 + k] - xv[k];
+        acc = fmaf(d, d, acc);
+      }
+    }
+  }
+  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float d = (float)theta[i] - x[i];
+    acc = fmaf(d, d, acc);
+  }
+  const float total = block_reduce_sum(acc, scratch);
+  if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+// dst = (alpha * coef) * (float(theta) - x), clip_state as clip_finalize
+// wrote it. A non-finite client ([2] == 0) stores +0.0 and never reads theta:
+// a uniform branch in front of the loop, so 0 * inf is never formed. w_out
+// (may be null) receives the weight this client contributes to W.
+template <typename T>
+__global__ void delta_scale_cast_kernel(float* __restrict__ dst,
+                                        const T* __restrict__ theta,
+                                        const float* __restrict__ x,
+                                        long long n, float alpha,
+                                        const float* __restrict__ clip_state,
+                                        float* __restrict__ w_out) {
+  using VT = VecTraits<T>;
+  constexpr int V = VT::kElems;
+  const long long nvec = n / V;
+  const bool finite = clip_state[2] != 0.f;
+  if (w_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
+    w_out[0] = finite ? alpha : 0.f;
+  if (!finite) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+         i < nvec; i += (long long)gridDim.x * blockDim.x) {
+#pragma unroll
+      for (int q = 0; q < V / 4; ++q)
+        reinterpret_cast<f32x4*>(dst)[i * (V / 4) + q] = f32x4{};
+    }
+    for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x +
+                       threadIdx.x;
+         i < n; i += (long long)gridDim.x * blockDim.x)
+      dst[i] = 0.f;
+    return;
+  }
+  const float s = alpha * clip_state[1];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
+       i += (long long)gridDim.x * blockDim.x) {
+    float tf[V];
+    VT::to_float(reinterpret_cast<const typename VT::VecT*>(theta)[i], tf);
+#pragma unroll
+    for (int q = 0; q < V / 4; ++q) {
+      const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i * (V / 4) + q];
+      f32x4 o;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = s * (tf[q * 4 + k] - xv[k]);
+      reinterpret_cast<f32x4*>(dst)[i * (V / 4) + q] = o;
+    }
+  }
+  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       i < n; i += (long long)gridDim.x * blockDim.x)
+    dst[i] = s * ((float)theta[i] - x[i]);
+}
+
+// ---- server side -----------------------------------------------------------
+
+// One thread: the reduced participation W -> round_state
+//   [0] W  [1] inv_W = 1 / W in fp64, rounded once (0 on a skipped round)
+//   [2] 1.0 applied / 0.0 skipped  [3] skipped rounds so far
+// [3] is only ever incremented here.
+__global__ void fedopt_finalize_kernel(const float* __restrict__ w_sum,
+                                       float* __restrict__ round_state) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const float W = w_sum[0];
+  const bool applied = isfinite(W) && W > 0.f;
+  const float skipped = round_state[3];
+  round_state[0] = W;
+  round_state[1] = applied ? (float)(1.0 / (double)W) : 0.f;
+  round_state[2] = applied ? 1.f : 0.f;
+  round_state[3] = applied ? skipped : skipped + 1.f;
+}
+
+enum ServerMode : int {
+  kServerMean = 0,     // x += Delta (float buffers; no momentum)
+  kServerAvgM = 1,
+  kServerAdagrad = 2,
+  kServerAdam = 3,
+  kServerYogi = 4,
+};
+
+// One element of the server step: Delta = D * inv_W, then MODE's update of
+// x, m, v (no bias correction, as in the paper).
+template <int MODE>
+DEVINL void server_update(float D, float inv_w, float& x, float& m, float& v,
+                          float lr, float b1, float b2, float tau) {
+  const float delta = D * inv_w;
+  if constexpr (MODE == kServerMean) {
+    x = x + delta;
+  } else if constexpr (MODE == kServerAvgM) {
+    m = fmaf(b1, m, delta);
+    x = fmaf(lr, m, x);
+  } else {
+    m = fmaf(b1, m, (1.f - b1) * delta);
+    if constexpr (MODE == kServerAdagrad) {
+      v = fmaf(delta, delta, v);
+    } else if constexpr (MODE == kServerAdam) {
+      v = fmaf(b2, v, (1.f - b2) * delta * delta);
+    } else {
+      const float d2 = delta * delta;
+      const float diff = v - d2;
+      const float sign = (float)(diff > 0.f) - (float)(diff < 0.f);
+      v = v - (1.f - b2) * d2 * sign;
+    }
+    x = fmaf(lr, m / (sqrtf(v) + tau), x);
+  }
+}
+
+// x, m, v updated in place from the reduced D. round_state[2] == 0 is a
+// uniform early exit: a skipped round writes nothing. Mean takes null m and
+// v, AvgM null v.
+template <int MODE>
+__global__ void server_step_kernel(const float* __restrict__ D,
+                                   float* __restrict__ x, float* __restrict__ m,
+                                   float* __restrict__ v, long long n, float lr,
+                                   float b1, float b2, float tau,
+                                   const float* __restrict__ round_state) {
+  constexpr bool HAS_M = MODE != kServerMean;
+  constexpr bool HAS_V = MODE >= kServerAdagrad;
+  if (round_state[2] == 0.f) return;
+  const float inv_w = round_state[1];
+  const long long nvec = n / 4;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
+       i += (long long)gridDim.x * blockDim.x) {
+    const f32x4 dv = reinterpret_cast<const f32x4*>(D)[i];
+    f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
+    f32x4 mv = {}, vv = {};
+    if constexpr (HAS_M) mv = reinterpret_cast<const f32x4*>(m)[i];
+    if constexpr (HAS_V) vv = reinterpret_cast<const f32x4*>(v)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float xk = xv[k], mk = mv[k], vk = vv[k];
+      server_update<MODE>(dv[k], inv_w, xk, mk, vk, lr, b1, b2, tau);
+      xv[k] = xk; mv[k] = mk; vv[k] = vk;
+    }
+    reinterpret_cast<f32x4*>(x)[i] = xv;
+    if constexpr (HAS_M) reinterpret_cast<f32x4*>(m)[i] = mv;
+    if constexpr (HAS_V) reinterpret_cast<f32x4*>(v)[i] = vv;
+  }
+  for (long long i = nvec * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       i < n; i += (long long)gridDim.x * blockDim.x) {
+    float xk = x[i], mk = 0.f, vk = 0.f;
+    if constexpr (HAS_M) mk = m[i];
+    if constexpr (HAS_V) vk = v[i];
+    server_update<MODE>(D[i], inv_w, xk, mk, vk, lr, b1, b2, tau);
+    x[i] = xk;
+    if constexpr (HAS_M) m[i] = mk;
+    if constexpr (HAS_V) v[i] = vk;
+  }
+}
+
+// ---- launchers -------------------------------------------------------------
+#include "launchers.h"
+
+int launch_delta_sumsq(bool is_bf16, const void* theta, const float* x,
+                       long long n, float* partials, hipStream_t s) {
+  const int grid = optim_grid(n);
+  if (is_bf16)
+    hipLaunchKernelGGL(delta_sumsq_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
+                       (const bf16*)theta, x, n, partials);
+  else
+    hipLaunchKernelGGL(delta_sumsq_kernel<float>, dim3(grid), dim3(kBlock), 0,
+                       s, (const float*)theta, x, n, partials);
+  return grid;
+}
+
+void launch_delta_scale_cast(bool is_bf16, float* dst, const void* theta,
+                             const float* x, long long n, float alpha,
+                             const float* clip_state, float* w_out,
+                             hipStream_t s) {
+  const int grid = optim_grid(n);
+  if (is_bf16)
+    hipLaunchKernelGGL(delta_scale_cast_kernel<bf16>, dim3(grid), dim3(kBlock),
+                       0, s, dst, (const bf16*)theta, x, n, alpha, clip_state,
+                       w_out);
+  else
+    hipLaunchKernelGGL(delta_scale_cast_kernel<float>, dim3(grid), dim3(kBlock),
+                       0, s, dst, (const float*)theta, x, n, alpha, clip_state,
+                       w_out);
+}
+
+void launch_fedopt_finalize(const float* w_sum, float* round_state,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(fedopt_finalize_kernel, dim3(1), dim3(1), 0, s, w_sum,
+                     round_state);
+}
+
+void launch_server_step(int mode, const float* D, float* x, float* m, float* v,
+                        long long n, float lr, float b1, float b2, float tau,
+                        const float* round_state, hipStream_t s) {
+  const int grid = optim_grid(n);
+#define BATON_SERVER_STEP(MODE)                                              \
+  hipLaunchKernelGGL(server_step_kernel<MODE>, dim3(grid), dim3(kBlock), 0, \
+                     s, D, x, m, v, n, lr, b1, b2, tau, round_state)
+  switch (mode) {
+    case kServerMean: BATON_SERVER_STEP(kServerMean); break;
+    case kServerAvgM: BATON_SERVER_STEP(kServerAvgM); break;
+    case kServerAdagrad: BATON_SERVER_STEP(kServerAdagrad); break;
+    case kServerAdam: BATON_SERVER_STEP(kServerAdam); break;
+    default: BATON_SERVER_STEP(kServerYogi); break;
+  }
+#undef BATON_SERVER_STEP
+}

@@ -43,6 +43,27 @@ void launch_cast_copy(bool dst_bf16, void* dst, const float* src, long long n,
 void launch_axpby(float* y, const float* x, long long n, float a, float b,
                   hipStream_t s);
 
+// fedopt.hip — the federated server step. All of x, m, v, D, dst, partials,
+// clip_state, w_sum / w_out and round_state are fp32; theta is fp32 or bf16.
+// One fp32 partial per block of sum (float(theta) - x)^2 at
+// partials[0 .. grid); returns the grid (optim_grid(n)).
+int launch_delta_sumsq(bool is_bf16, const void* theta, const float* x,
+                       long long n, float* partials, hipStream_t s);
+// dst = (alpha * clip_state[1]) * (float(theta) - x), or +0.0 without a read
+// of theta when clip_state[2] == 0; w_out (may be null) = alpha or 0.
+void launch_delta_scale_cast(bool is_bf16, float* dst, const void* theta,
+                             const float* x, long long n, float alpha,
+                             const float* clip_state, float* w_out,
+                             hipStream_t s);
+// round_state[4] = [W, 1 / W or 0, applied 1 / 0, skipped rounds] from w_sum[0]
+void launch_fedopt_finalize(const float* w_sum, float* round_state,
+                            hipStream_t s);
+// mode: 0 mean (m, v null), 1 fedavgm (v null), 2 fedadagrad, 3 fedadam,
+// 4 fedyogi. Updates x, m, v in place; nothing when round_state[2] == 0.
+void launch_server_step(int mode, const float* D, float* x, float* m, float* v,
+                        long long n, float lr, float b1, float b2, float tau,
+                        const float* round_state, hipStream_t s);
+
 // loss.hip
 void launch_mse_fwd(bool is_bf16, const void* x, const void* y, float* out,
                     long long n, hipStream_t s);

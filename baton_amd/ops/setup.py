@@ -20,6 +20,7 @@ SRC = [
         "bindings.cpp",
         "optim.hip",
         "fedmath.hip",
+        "fedopt.hip",
         "loss.hip",
         "norm.hip",
         "elementwise.hip",

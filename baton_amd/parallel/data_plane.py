@@ -29,6 +29,13 @@ Numerics: the reduce runs in fp32 regardless of model dtype (config
 reduce_dtype), so the result is comparable against the CPU/HTTP FedAvg
 oracle; tests assert near-bit-exact agreement in fp32.
 
+Server optimizer (`enable_server_opt` + `fedopt_arena`, off by default): the
+ranks send clipped updates w_i c_i (theta_i - x) against an fp32 master x
+where FedAvg sends parameters, rank 0 applies FedAvgM / FedAdagrad / FedAdam /
+FedYogi to x between the reduce and the broadcast (ops/csrc/fedopt.hip), and
+every rank installs x. Same streams, buckets and fence; the definition and
+the CPU oracle are in fed/server_opt.py.
+
 CPU testing: the same class runs on gloo with world_size>1 (reduce/broadcast
 are identical calls), which is how tests/test_data_plane.py exercises the
 distributed path without a GPU.
@@ -104,6 +111,8 @@ class FederatedDataPlane:
         self.pending: Optional[PendingAggregation] = None
         # (graph, captured weights, captured n_samples) from capture_aggregation
         self._agg_graph = None
+        # state of fedopt_arena (enable_server_opt); None = plain FedAvg
+        self._fedopt: Optional[dict] = None
 
     def _init_from_env(self) -> None:
         backend = self.config.backend
@@ -332,6 +341,271 @@ class FederatedDataPlane:
             self.fedavg_flat(g.flat, n_samples, weights=weights)
         # integer buffers: copy from the heaviest rank (deterministic
         # tie-break: lowest rank wins, matching fed.aggregate)
+        for b in int_bufs:
+            t = b.detach()
+            if dist.get_backend() == "gloo" and t.device.type != "cpu":
+                cpu = t.cpu()
+                dist.broadcast(cpu, src=heaviest)
+                t.copy_(cpu)
+            else:
+                dist.broadcast(t, src=heaviest)
+        return weights
+
+    # -- server optimizer over clipped client updates ---------------------------
+
+    def _arena_on_gpu(self, arena: FlatParamArena) -> bool:
+        return (
+            self.device.type == "cuda"
+            and dist.get_backend() != "gloo"
+            and all(g.flat.device == self.device for g in arena.all_groups)
+        )
+
+    def enable_server_opt(self, arena: FlatParamArena, cfg) -> None:
+        """Allocate the state of ``fedopt_arena`` for ``arena`` (a collective:
+        every rank calls it). Per dtype group: the fp32 master ``x`` and an
+        fp32 reduce buffer on every rank, ``m`` and ``v`` on rank 0 only;
+        once: ``partials``, ``clip_state``, ``w_slot``, ``round_state``.
+        ``x`` is initialised from the arena and broadcast from rank 0, so
+        all ranks start equal. Nothing is allocated per round. ``cfg`` is a
+        ServerOptConfig with a name other than 'none'."""
+        from baton_amd.fed import server_opt as so
+
+        so.validate(cfg.name, cfg.lr, cfg.beta1, cfg.beta2, cfg.tau,
+                    cfg.client_clip_norm)
+        if cfg.name == "none":
+            raise ValueError("enable_server_opt: server_opt.name is 'none'")
+        on_gpu = self._arena_on_gpu(arena)
+        dev = self.device if on_gpu else torch.device("cpu")
+        f32 = dict(dtype=torch.float32, device=dev)
+        groups = []
+        n_blocks = 0
+        for i, g in enumerate(arena.all_groups):
+            n = g.flat.numel()
+            x = g.flat.detach().reshape(-1).to(**f32).clone()
+            dist.broadcast(x, src=0)
+            mode = cfg.name if i < len(arena.groups) else so.MEAN
+            m = v = None
+            if self.rank == 0 and mode != so.MEAN:
+                m = torch.zeros(n, **f32)
+                if mode in so.ADAPTIVE:
+                    v = torch.full((n,), so.f32(so.f32(cfg.tau) ** 2), **f32)
+            groups.append(dict(mode=mode, x=x, buf=torch.empty(n, **f32),
+                               m=m, v=v))
+            if on_gpu:
+                from baton_amd.ops._ext import require_hip
+
+                n_blocks += require_hip().optim_grid(n)
+        self._fedopt = dict(
+            arena=arena,
+            on_gpu=on_gpu,
+            name=cfg.name,
+            lr=so.f32(cfg.lr), b1=so.f32(cfg.beta1), b2=so.f32(cfg.beta2),
+            tau=so.f32(cfg.tau),
+            clip=float(cfg.client_clip_norm) if cfg.client_clip_norm > 0
+            else float("inf"),
+            groups=groups,
+            partials=torch.zeros(max(n_blocks, 1), **f32),
+            clip_state=torch.zeros(4, **f32),
+            w_slot=torch.zeros(1, **f32),
+            round_state=torch.zeros(4, **f32),
+        )
+
+    @property
+    def server_opt_enabled(self) -> bool:
+        return self._fedopt is not None
+
+    @property
+    def fedopt_clip_state(self) -> torch.Tensor:
+        """This rank's [norm, coef, finite, non-finite rounds so far]."""
+        return self._fedopt["clip_state"]
+
+    @property
+    def fedopt_round_state(self) -> torch.Tensor:
+        """[W, 1 / W or 0, applied 1 / 0, skipped rounds], equal on all ranks."""
+        return self._fedopt["round_state"]
+
+    def server_opt_state(self) -> "dict[str, torch.Tensor]":
+        """CPU copies of this rank's state: ``x.<group>`` and ``round_state``
+        everywhere, ``m.<group>`` / ``v.<group>`` on rank 0."""
+        st = self._fedopt
+        out = {"round_state": st["round_state"].detach().cpu().clone()}
+        for i, gs in enumerate(st["groups"]):
+            for key in ("x", "m", "v"):
+                if gs[key] is not None:
+                    out[f"{key}.{i}"] = gs[key].detach().cpu().clone()
+        return out
+
+    def load_server_opt_state(self, state: "dict[str, torch.Tensor]") -> None:
+        """Restore what ``server_opt_state`` returned on rank 0 (a collective:
+        ``x`` and ``round_state`` are re-broadcast from rank 0, whose ``state``
+        is the one that counts)."""
+        st = self._fedopt
+        if self.rank == 0:
+            st["round_state"].copy_(state["round_state"])
+        dist.broadcast(st["round_state"], src=0)
+        for i, gs in enumerate(st["groups"]):
+            if self.rank == 0:
+                for key in ("x", "m", "v"):
+                    if gs[key] is not None:
+                        gs[key].copy_(state[f"{key}.{i}"])
+            dist.broadcast(gs["x"], src=0)
+
+    def _fedopt_gpu_sequence(self, arena: FlatParamArena, alpha: float) -> None:
+        """The device side of a round, enqueued on the CALLER's current
+        stream. No host read: the clip coefficient, the participation and the
+        skip decision stay in clip_state / w_slot / round_state.
+
+          1. delta_sumsq per group, one clip_finalize
+          2. delta_scale_cast of the first bucket, which writes w_slot
+          3. reduce w_slot, fedopt_finalize on rank 0, broadcast round_state
+          4. per bucket: delta_scale_cast, async reduce; on rank 0 wait()
+             on that reduce (a stream fence) and server_step on the bucket;
+             async broadcast of the x bucket; then cast_copy(theta, x)
+
+        Every reduce Work is kept and waited on, on every rank: nothing here
+        relies on the communicator running reduce and broadcast of one
+        buffer in issue order."""
+        from baton_amd.ops._ext import require_hip
+
+        ops = require_hip()
+        st = self._fedopt
+        root = self.rank == 0
+        clip_state, w_slot, round_state = (
+            st["clip_state"], st["w_slot"], st["round_state"])
+        thetas = [g.flat.detach().reshape(-1) for g in arena.all_groups]
+        with trace_scope("fedopt_norm"):
+            off = 0
+            for theta, gs in zip(thetas, st["groups"]):
+                off += ops.delta_sumsq(theta, gs["x"], st["partials"], off)
+            ops.clip_finalize(st["partials"], off, st["clip"], clip_state)
+        buckets = [
+            (gi, lo, min(lo + _BUCKET_ELEMS, theta.numel()))
+            for gi, theta in enumerate(thetas)
+            for lo in range(0, theta.numel(), _BUCKET_ELEMS)
+        ]
+        with trace_scope("fedopt_reduce_step_bcast"):
+            gi, lo, hi = buckets[0]
+            gs = st["groups"][gi]
+            ops.delta_scale_cast(gs["buf"][lo:hi], thetas[gi][lo:hi],
+                                 gs["x"][lo:hi], alpha, clip_state, w_slot)
+            dist.reduce(w_slot, dst=0, op=dist.ReduceOp.SUM,
+                        async_op=True).wait()
+            if root:
+                ops.fedopt_finalize(w_slot, round_state)
+            dist.broadcast(round_state, src=0, async_op=True).wait()
+            bcast_works = []
+            for k, (gi, lo, hi) in enumerate(buckets):
+                gs = st["groups"][gi]
+                piece = gs["buf"][lo:hi]
+                if k > 0:
+                    ops.delta_scale_cast(piece, thetas[gi][lo:hi],
+                                         gs["x"][lo:hi], alpha, clip_state,
+                                         None)
+                reduce_work = dist.reduce(piece, dst=0, op=dist.ReduceOp.SUM,
+                                          async_op=True)
+                reduce_work.wait()      # stream-level fence only
+                if root:
+                    ops.server_step(
+                        gs["mode"], piece, gs["x"][lo:hi],
+                        None if gs["m"] is None else gs["m"][lo:hi],
+                        None if gs["v"] is None else gs["v"][lo:hi],
+                        st["lr"], st["b1"], st["b2"], st["tau"], round_state)
+                bcast_works.append(
+                    dist.broadcast(gs["x"][lo:hi], src=0, async_op=True))
+            for (gi, lo, hi), w in zip(buckets, bcast_works):
+                w.wait()
+                ops.cast_copy(thetas[gi][lo:hi], st["groups"][gi]["x"][lo:hi])
+
+    def _fedopt_cpu_sequence(self, arena: FlatParamArena, alpha: float) -> None:
+        """The same round with torch ops (gloo / CPU): the arithmetic of
+        fed.server_opt, the collectives of the device sequence."""
+        from baton_amd.fed import server_opt as so
+
+        st = self._fedopt
+        root = self.rank == 0
+        cpu32 = dict(device="cpu", dtype=torch.float32)
+        thetas = [g.flat.detach().reshape(-1) for g in arena.all_groups]
+        deltas = [t.to(**cpu32) - gs["x"] for t, gs in zip(thetas, st["groups"])]
+        sumsq = sum(float(d.double().pow(2).sum()) for d in deltas)
+        norm, coef, finite = so.clip_coef(sumsq, st["clip"])
+        cs = st["clip_state"]
+        cs[0], cs[1], cs[2] = norm, coef, float(finite)
+        if not finite:
+            cs[3] += 1.0
+        s = torch.tensor(alpha, dtype=torch.float32) * torch.tensor(
+            coef, dtype=torch.float32)
+        st["w_slot"][0] = alpha if finite else 0.0
+        dist.reduce(st["w_slot"], dst=0, op=dist.ReduceOp.SUM)
+        rs = st["round_state"]
+        if root:
+            W = st["w_slot"][0].item()
+            inv_w, applied = so.inv_weight(W)
+            rs[0], rs[1], rs[2] = W, inv_w, float(applied)
+            if not applied:
+                rs[3] += 1.0
+        dist.broadcast(rs, src=0)
+        for theta, d, gs in zip(thetas, deltas, st["groups"]):
+            if finite:
+                torch.mul(d, s, out=gs["buf"])
+            else:
+                gs["buf"].zero_()      # theta's NaN never meets the 0 weight
+            dist.reduce(gs["buf"], dst=0, op=dist.ReduceOp.SUM)
+            if root and rs[2].item() != 0.0:
+                so.server_update_(gs["mode"], gs["buf"], rs[1].item(), gs["x"],
+                                  gs["m"], gs["v"], st["lr"], st["b1"],
+                                  st["b2"], st["tau"])
+            dist.broadcast(gs["x"], src=0)
+            theta.copy_(gs["x"].to(theta.dtype))
+
+    def fedopt_arena(
+        self, arena: FlatParamArena, n_samples: int, async_handle: bool = False
+    ) -> torch.Tensor:
+        """One federated round through the server optimizer configured by
+        ``enable_server_opt``: every rank sends its clipped update
+        ``w_i c_i (theta_i - x)``, rank 0 steps the fp32 master ``x`` (and
+        ``m``, ``v``), and every rank installs the broadcast ``x`` in its
+        arena's dtype. A rank whose update is not finite sends zeros and
+        weight 0; a round without any finite update leaves x, m and v as they
+        were and still resets every rank to x. Integer buffers come from the
+        heaviest client. The stream, side-stream and ``PendingAggregation``
+        protocol is ``fedavg_arena``'s; the returned value is the weight
+        vector."""
+        st = self._fedopt
+        if st is None or st["arena"] is not arena:
+            raise RuntimeError(
+                "fedopt_arena: call enable_server_opt(arena, cfg) first")
+        from baton_amd.fed.server_opt import f32
+
+        weights = self.gather_weights(n_samples)
+        total = float(weights.sum().item())
+        if total <= 0:
+            raise ValueError("total sample weight must be positive")
+        alpha = f32(float(n_samples) / total)
+        heaviest = int(torch.argmax(weights).item())
+        int_bufs = [
+            b for _, b in arena.model.named_buffers() if not b.is_floating_point()
+        ]
+        self.pending = PendingAggregation(weights)  # pre-fenced default
+
+        if st["on_gpu"] and self._side_stream is not None:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream())
+            with torch.cuda.stream(self._side_stream):
+                self._side_stream.wait_event(ev)
+                self._fedopt_gpu_sequence(arena, alpha)
+                for b in int_bufs:
+                    dist.broadcast(b.detach(), src=heaviest)
+                done = torch.cuda.Event()
+                done.record(self._side_stream)
+            self.pending = PendingAggregation(weights, done)
+            if not async_handle:
+                self.pending.wait()
+            return weights
+
+        if st["on_gpu"]:
+            self._fedopt_gpu_sequence(arena, alpha)
+        else:
+            self._fedopt_cpu_sequence(arena, alpha)
         for b in int_bufs:
             t = b.detach()
             if dist.get_backend() == "gloo" and t.device.type != "cpu":

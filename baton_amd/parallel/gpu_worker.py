@@ -59,7 +59,11 @@ class GPUExperimentWorker(ExperimentWorker):
         else:
             loss_history = self.model.train_round(*data, n_epoch=n_epoch)
         # ---- data plane: FedAvg over xGMI (all clients rendezvous here)
-        weights = self.plane.fedavg_arena(self.arena, n_samples)
+        if self.plane.server_opt_enabled:
+            # server optimizer over clipped updates (enable_server_opt)
+            weights = self.plane.fedopt_arena(self.arena, n_samples)
+        else:
+            weights = self.plane.fedavg_arena(self.arena, n_samples)
         loss_history = self.plane.weighted_mean_losses(loss_history, weights)
         return n_samples, [float(x) for x in loss_history]
 

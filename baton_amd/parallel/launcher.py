@@ -34,7 +34,9 @@ def client_main(args) -> None:
     from baton_amd.parallel.data_plane import FederatedDataPlane
     from baton_amd.parallel.gpu_worker import GPUExperimentWorker
     from baton_amd.runtime.arena import FlatParamArena
-    from baton_amd.utils.config import BatonConfig, DataPlaneConfig, TrainConfig
+    from baton_amd.utils.config import (
+        BatonConfig, DataPlaneConfig, ServerOptConfig, TrainConfig,
+    )
 
     rank = int(os.environ["RANK"])
     on_gpu = torch.cuda.is_available()
@@ -58,6 +60,13 @@ def client_main(args) -> None:
     torch.manual_seed(args.seed)  # identical global init on every client
     model = create_model(args.model, cfg.train).to(plane.device).to(dtype)
     arena = FlatParamArena(model)
+    if args.server_opt != "none":
+        b1, b2 = args.server_betas
+        cfg.server_opt = ServerOptConfig(
+            name=args.server_opt, lr=args.server_lr, beta1=b1, beta2=b2,
+            tau=args.server_tau, client_clip_norm=args.client_clip_norm,
+        )
+        plane.enable_server_opt(arena, cfg.server_opt)
 
     class Client(GPUExperimentWorker):
         def get_data(self):
@@ -170,6 +179,17 @@ def main() -> None:
                    help="clip the global gradient norm and skip non-finite "
                         "steps; 0 = off")
     p.add_argument("--fedprox-mu", type=float, default=0.0)
+    p.add_argument("--server-opt", default="none",
+                   choices=["none", "fedavgm", "fedadagrad", "fedadam",
+                            "fedyogi"],
+                   help="server step over clipped client updates on the data "
+                        "plane; none = plain FedAvg")
+    p.add_argument("--server-lr", type=float, default=1.0)
+    p.add_argument("--server-betas", type=float, nargs=2, default=(0.9, 0.99),
+                   metavar=("BETA1", "BETA2"))
+    p.add_argument("--server-tau", type=float, default=1e-3)
+    p.add_argument("--client-clip-norm", type=float, default=0.0,
+                   help="bound on each client's update norm; 0 = off")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--port", type=int, default=8080)
     p.add_argument("--dist-port", type=int, default=29531)

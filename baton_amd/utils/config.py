@@ -78,10 +78,36 @@ class DataPlaneConfig:
 
 
 @dataclass
+class ServerOptConfig:
+    """Server-side step over clipped client updates (fed/server_opt.py)."""
+
+    # 'none' (plain FedAvg, the code path without any of this) | 'fedavgm' |
+    # 'fedadagrad' | 'fedadam' | 'fedyogi'
+    name: str = "none"
+    lr: float = 1.0
+    beta1: float = 0.9
+    beta2: float = 0.99
+    tau: float = 1e-3                # adaptivity floor; v starts at tau^2
+    client_clip_norm: float = 0.0    # >0 bounds each client's update norm;
+                                     # 0 = off
+
+    def __post_init__(self):
+        from baton_amd.fed.server_opt import validate
+
+        validate(self.name, self.lr, self.beta1, self.beta2, self.tau,
+                 self.client_clip_norm)
+
+    @property
+    def enabled(self) -> bool:
+        return self.name != "none"
+
+
+@dataclass
 class BatonConfig:
     control: ControlPlaneConfig = field(default_factory=ControlPlaneConfig)
     train: TrainConfig = field(default_factory=TrainConfig)
     data_plane: DataPlaneConfig = field(default_factory=DataPlaneConfig)
+    server_opt: ServerOptConfig = field(default_factory=ServerOptConfig)
     checkpoint_dir: Optional[str] = None   # persist global model per round
     device: str = "cuda"                   # 'cuda' (= ROCm HIP) | 'cpu'
 
@@ -113,6 +139,8 @@ class BatonConfig:
             cfg.train = build(TrainConfig, raw["train"])
         if "data_plane" in raw:
             cfg.data_plane = build(DataPlaneConfig, raw["data_plane"])
+        if "server_opt" in raw:
+            cfg.server_opt = build(ServerOptConfig, raw["server_opt"])
         for k in ("checkpoint_dir", "device"):
             if k in raw:
                 setattr(cfg, k, raw[k])

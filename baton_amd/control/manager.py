@@ -19,6 +19,9 @@ Server optimizer: with ``config.server_opt.name`` other than 'none', the
 'fedavg' mode aggregates through fed.server_opt.ServerOptimizer (clipped
 client updates, FedAvgM / FedAdagrad / FedAdam / FedYogi on an fp32 master);
 its state is a sidecar ``<name>.server_opt.ckpt`` beside the checkpoint.
+With ``server_opt.dp_noise_multiplier`` > 0 the step adds DP-FedAvg noise;
+``dp_rounds`` and ``dp_epsilon`` appear in ``/metrics`` and ``dp_rounds`` is
+kept in the sidecar (the seed never is).
 
 Checkpoint/resume: the global model is persisted per round
 with the round-start payload schema {'state_dict', 'update_name', 'n_epoch'}
@@ -86,6 +89,7 @@ class Experiment:
         if self.server_opt is not None:
             self.metrics["skipped_rounds"] = 0
             self.metrics["last_round_W"] = 0.0
+            self._publish_dp_metrics()
         if app is not None:
             self.register_handlers(app)
 
@@ -292,6 +296,7 @@ class Experiment:
                 )
                 self.metrics["skipped_rounds"] = self.server_opt.skipped_rounds
                 self.metrics["last_round_W"] = self.server_opt.last_W
+                self._publish_dp_metrics()
             self.rounds.loss_history.extend(
                 weighted_loss_history(
                     [r["loss_history"] for r in responses.values()], weights
@@ -308,6 +313,14 @@ class Experiment:
             elapsed,
         )
         self._save_checkpoint()
+
+    def _publish_dp_metrics(self) -> None:
+        """``dp_rounds`` and ``dp_epsilon`` (at config.server_opt.dp_delta)
+        with DP noise on; the seed is never published."""
+        so = self.server_opt
+        if so is not None and so.noise_multiplier > 0:
+            self.metrics["dp_rounds"] = so.dp_rounds
+            self.metrics["dp_epsilon"] = so.epsilon
 
     # -- checkpoint / resume ---------------------------------------------------
 
@@ -377,6 +390,7 @@ class Experiment:
         self.server_opt.last_W = float(meta.get("last_round_W", 0.0))
         self.metrics["skipped_rounds"] = self.server_opt.skipped_rounds
         self.metrics["last_round_W"] = self.server_opt.last_W
+        self._publish_dp_metrics()
         return True
 
     def load_checkpoint(self) -> bool:

@@ -32,6 +32,55 @@ correction, m0 = 0, v0 = float32(tau * tau):
 Float buffers (BatchNorm statistics) take ``x = x + Delta`` with no momentum;
 integer buffers are copied from the heaviest client, as in ``fedavg_``.
 
+DP-FedAvg (McMahan et al., "Learning Differentially Private Recurrent
+Language Models"), off unless ``dp_noise_multiplier`` z > 0; it needs a server
+optimizer and a finite ``client_clip_norm`` C > 0. With w_i as above:
+
+    sigma  = float32(z * C * max_i w_i)      (float64 on the host, rounded once)
+    xi[e]  = fl(sigma * zeta[e])             zeta: the unit normal of element e
+    Delta  = fl(D + xi)                      fixed denominator: NO multiply by inv_W
+
+and Delta enters the unchanged step of each mode; float buffers are part of
+the clipped norm, so they take the noise too. The denominator is the nominal
+total weight 1 (DP-FedAvg's fixed-denominator estimator), so the number of
+finite clients, which depends on the data, does not scale the released value.
+A round with W not > 0 is still skipped and writes nothing. ``max_i w_i``
+comes from the weights the host already holds.
+
+Unit normals: Philox4x32-10 with the Random123 constants (multipliers
+0xD2511F53, 0xCD9E8D57; Weyl increments 0x9E3779B9, 0xBB67AE85). For flat
+element index e within noise stream s, in round t:
+
+    block j = e >> 2,  counter = (lo32(j), hi32(j), lo32(t), s),
+    key = (lo32(seed), hi32(seed)),  output (r0, r1, r2, r3)
+    u1 = ((r0 >> 8) + 1) * 2^-24 in (0, 1],  u2 = (r1 >> 8) * 2^-24 in [0, 1)
+    R = sqrtf(-2 logf(u1)),  zeta0 = R cospif(2 u2),  zeta1 = R sinpif(2 u2)
+    zeta2, zeta3 likewise from (r2, r3); element e takes lane e & 3.
+
+t counts every call of the round, skipped rounds included, so a (seed, t, s, e)
+tuple is never reused. On the data plane s is the ordinal of the group in
+``arena.all_groups`` and e the flat offset in the group; in ``ServerOptimizer``
+s is the ordinal of the key among the float keys of ``global_sd`` and e the
+offset in the tensor. The device evaluates the normals in fp32
+(ops/csrc/fedopt.hip); the oracle here evaluates them in float64 from the same
+integers (``unit_normals``) and rounds once to fp32.
+
+Accounting: every registered client takes part in every round, so there is no
+subsampling amplification. After T rounds, Renyi composition of the Gaussian
+mechanism, min over alpha of alpha T / (2 z^2) + ln(1/delta) / (alpha - 1),
+has the closed form ``privacy_spent``:
+
+    eps(delta) = T / (2 z^2) + sqrt(2 T ln(1/delta)) / z
+
+Limits of the guarantee, plainly: the client weights n_i are treated as
+public. The skip of non-finite clients and of a whole round, and the integer
+buffers copied from the heaviest client, are outside the guarantee. Philox is
+not a cryptographic generator. The normal is a 24-bit discretisation truncated
+at |zeta| <= sqrt(48 ln 2) ~ 5.77, and floating-point attacks on it are not
+addressed. This is the level of the common DP training libraries in their
+default mode, not a hardened one. The seed is never written to disk or to
+metrics.
+
 This module is the CPU oracle of that definition (``ServerOptimizer.step_``,
 what the HTTP manager runs) and holds the elementwise helpers the gloo branch
 of the data plane shares; the HIP kernels (ops/csrc/fedopt.hip) run the same
@@ -44,9 +93,11 @@ of the sum.
 from __future__ import annotations
 
 import math
+import secrets
 from collections import OrderedDict
 from typing import Dict, Iterable, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 MODES = ("fedavgm", "fedadagrad", "fedadam", "fedyogi")
@@ -87,12 +138,110 @@ def inv_weight(W: float):
     return (f32(1.0 / W) if applied else 0.0), applied
 
 
+# ---- DP noise: Philox4x32-10, the unit normals and the accounting -------------
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_MASK32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 (Random123). ``counter`` is four and ``key`` two 32-bit
+    words, each an int or an integer array (broadcast together); returns the
+    four output words as uint32 arrays."""
+    c = [np.asarray(w, dtype=np.uint64) & _MASK32 for w in counter]
+    k = [np.asarray(w, dtype=np.uint64) & _MASK32 for w in key]
+    if len(c) != 4 or len(k) != 2:
+        raise ValueError("philox4x32 takes a 4-word counter and a 2-word key")
+    m0, m1 = np.uint64(_PHILOX_M0), np.uint64(_PHILOX_M1)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]          # 32 x 32 -> 64 bits, exact
+        c = [(p1 >> s32) ^ c[1] ^ k[0], p1 & _MASK32,
+             (p0 >> s32) ^ c[3] ^ k[1], p0 & _MASK32]
+        k = [(k[0] + np.uint64(_PHILOX_W0)) & _MASK32,
+             (k[1] + np.uint64(_PHILOX_W1)) & _MASK32]
+    return tuple(w.astype(np.uint32) for w in c)
+
+
+def _box_muller64(a: np.ndarray, b: np.ndarray):
+    """The two normals of the words (a, b), in float64. cospi and sinpi are
+    reduced by quadrant first, so their exact zeros are exact here too."""
+    u1 = ((a >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+    t = (b >> np.uint32(8)).astype(np.float64) * 2.0 ** -23     # 2 u2, exact
+    with np.errstate(divide="ignore"):
+        R = np.sqrt(-2.0 * np.log(u1))
+    q = np.floor(2.0 * t)
+    r = t - 0.5 * q                                              # [0, 1/2)
+    c, s = np.cos(np.pi * r), np.sin(np.pi * r)
+    cos = np.select([q == 0, q == 1, q == 2], [c, -s, -c], s)
+    sin = np.select([q == 0, q == 1, q == 2], [s, c, -s], -c)
+    return R * cos, R * sin
+
+
+def unit_normals(seed: int, round: int, stream: int, offset: int,
+                 n: int) -> np.ndarray:
+    """zeta[offset .. offset + n) of stream ``stream`` in round ``round``:
+    float64 from the integers the device uses (the module docstring)."""
+    seed, round, stream, offset, n = (int(seed), int(round), int(stream),
+                                      int(offset), int(n))
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+    if round < 0 or not 0 <= stream < 2 ** 32 or offset < 0 or n < 0:
+        raise ValueError("round, offset and n must be >= 0 and stream in "
+                         "[0, 2^32)")
+    if n == 0:
+        return np.zeros(0, np.float64)
+    j = np.arange(offset >> 2, ((offset + n - 1) >> 2) + 1, dtype=np.uint64)
+    r = philox4x32((j & _MASK32, j >> np.uint64(32), round & 0xFFFFFFFF,
+                    stream), (seed & 0xFFFFFFFF, seed >> 32))
+    z = np.stack(_box_muller64(r[0], r[1]) + _box_muller64(r[2], r[3]), axis=1)
+    lo = offset & 3
+    return np.ascontiguousarray(z.reshape(-1)[lo: lo + n])
+
+
+def privacy_spent(rounds: int, noise_multiplier: float,
+                  delta: float) -> float:
+    """eps(delta) after ``rounds`` full-participation rounds with noise
+    multiplier z: T / (2 z^2) + sqrt(2 T ln(1/delta)) / z, in float64."""
+    T, z = float(rounds), float(noise_multiplier)
+    if not 0.0 < delta < 1.0:
+        raise ValueError(f"delta must be in (0, 1), got {delta}")
+    if T < 0 or not z >= 0:
+        raise ValueError("rounds and noise_multiplier must be >= 0")
+    if T == 0:
+        return 0.0
+    if z == 0:
+        return math.inf
+    return T / (2.0 * z * z) + math.sqrt(2.0 * T * math.log(1.0 / delta)) / z
+
+
+def dp_sigma(noise_multiplier: float, clip_norm: float,
+             max_weight: float) -> float:
+    """sigma = float32(z C max_i w_i), the product in float64."""
+    return f32(float(noise_multiplier) * float(clip_norm) * float(max_weight))
+
+
+def dp_xi(seed: int, round: int, stream: int, offset: int, n: int,
+          sigma: float) -> torch.Tensor:
+    """xi = fl(sigma * fl(zeta)) as an fp32 tensor of n elements."""
+    zeta = torch.from_numpy(unit_normals(seed, round, stream, offset, n))
+    return _t(sigma) * zeta.float()
+
+
 def server_update_(mode: str, D: torch.Tensor, inv_w: float, x: torch.Tensor,
                    m: Optional[torch.Tensor], v: Optional[torch.Tensor],
                    lr: float, b1: float, b2: float, tau: float) -> None:
     """One applied server step on fp32 tensors, in place; lr, b1, b2, tau are
     fp32-valued. The order of operations is server_step_kernel's."""
-    delta = D * _t(inv_w)
+    server_apply_(mode, D * _t(inv_w), x, m, v, lr, b1, b2, tau)
+
+
+def server_apply_(mode: str, delta: torch.Tensor, x: torch.Tensor,
+                  m: Optional[torch.Tensor], v: Optional[torch.Tensor],
+                  lr: float, b1: float, b2: float, tau: float) -> None:
+    """The step of ``server_update_`` from Delta itself (fl(D inv_W), or
+    fl(D + xi) with DP noise)."""
     if mode == MEAN:
         x.add_(delta)
         return
@@ -115,7 +264,8 @@ def server_update_(mode: str, D: torch.Tensor, inv_w: float, x: torch.Tensor,
 
 
 def validate(name: str, lr: float, beta1: float, beta2: float, tau: float,
-             client_clip_norm: float) -> None:
+             client_clip_norm: float, dp_noise_multiplier: float = 0.0,
+             dp_seed: Optional[int] = None, dp_delta: float = 1e-5) -> None:
     if name != "none" and name not in MODES:
         raise ValueError(
             f"unknown server optimizer {name!r} (none, {', '.join(MODES)})")
@@ -130,16 +280,53 @@ def validate(name: str, lr: float, beta1: float, beta2: float, tau: float,
         raise ValueError(
             f"server_opt.client_clip_norm must be >= 0 (0 = off), got "
             f"{client_clip_norm}")
+    z = dp_noise_multiplier
+    if z == 0:
+        return
+    if not (z > 0 and math.isfinite(z)):
+        raise ValueError(
+            f"server_opt.dp_noise_multiplier must be finite and >= 0, got {z}")
+    if name == "none":
+        raise ValueError(
+            "server_opt.dp_noise_multiplier > 0 needs a server optimizer "
+            "(name is 'none')")
+    if not (client_clip_norm > 0 and math.isfinite(client_clip_norm)):
+        raise ValueError(
+            "server_opt.dp_noise_multiplier > 0 needs a finite "
+            f"client_clip_norm > 0, got {client_clip_norm}")
+    if not 0.0 < dp_delta < 1.0:
+        raise ValueError(
+            f"server_opt.dp_delta must be in (0, 1), got {dp_delta}")
+    if dp_seed is not None and not (
+            isinstance(dp_seed, int) and 0 <= dp_seed < 2 ** 64):
+        raise ValueError(
+            f"server_opt.dp_seed must be an integer in [0, 2^64), got "
+            f"{dp_seed}")
+
+
+def resolve_seed(dp_seed: Optional[int]) -> int:
+    """``dp_seed``, or a fresh 64-bit seed from ``secrets`` for None."""
+    return secrets.randbits(64) if dp_seed is None else int(dp_seed)
 
 
 class ServerOptimizer:
     """The server step on CPU state dicts, with its own fp32 master copy of
-    every float tensor. ``client_clip_norm`` 0 (or inf) means no clipping."""
+    every float tensor. ``client_clip_norm`` 0 (or inf) means no clipping.
+    ``noise_multiplier`` > 0 turns DP-FedAvg on (the module docstring):
+    ``seed`` None draws a fresh one, ``dp_rounds`` counts the calls of
+    ``step_`` made with it, skipped rounds included."""
 
     def __init__(self, name: str = "fedavgm", lr: float = 1.0,
                  beta1: float = 0.9, beta2: float = 0.99, tau: float = 1e-3,
-                 client_clip_norm: float = 0.0):
-        validate(name, lr, beta1, beta2, tau, client_clip_norm)
+                 client_clip_norm: float = 0.0, noise_multiplier: float = 0.0,
+                 seed: Optional[int] = None, delta: float = 1e-5):
+        validate(name, lr, beta1, beta2, tau, client_clip_norm,
+                 noise_multiplier, seed, delta)
+        self.noise_multiplier = float(noise_multiplier)
+        self.delta = float(delta)
+        self.seed = resolve_seed(seed) if self.noise_multiplier > 0 else None
+        self.dp_rounds = 0
+        self.last_sigma = 0.0
         if name == "none":
             raise ValueError("'none' is plain FedAvg: there is no optimizer")
         self.name = name
@@ -167,7 +354,15 @@ class ServerOptimizer:
         if cfg is None or cfg.name == "none":
             return None
         return cls(cfg.name, cfg.lr, cfg.beta1, cfg.beta2, cfg.tau,
-                   cfg.client_clip_norm)
+                   cfg.client_clip_norm, cfg.dp_noise_multiplier, cfg.dp_seed,
+                   cfg.dp_delta)
+
+    @property
+    def epsilon(self) -> float:
+        """eps(delta) spent so far; 0.0 with DP off."""
+        if self.noise_multiplier <= 0:
+            return 0.0
+        return privacy_spent(self.dp_rounds, self.noise_multiplier, self.delta)
 
     # -- state -----------------------------------------------------------------
 
@@ -185,10 +380,13 @@ class ServerOptimizer:
 
     def state_dict(self) -> "OrderedDict[str, torch.Tensor]":
         """Flat tensors: ``x.<key>``, ``m.<key>``, ``v.<key>`` and the
-        0-dim int64 ``skipped_rounds``."""
+        0-dim int64 ``skipped_rounds``; with DP noise on, the 0-dim int64
+        ``dp_rounds`` as well (never the seed)."""
         out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
         out["skipped_rounds"] = torch.tensor(self.skipped_rounds,
                                              dtype=torch.int64)
+        if self.noise_multiplier > 0:
+            out["dp_rounds"] = torch.tensor(self.dp_rounds, dtype=torch.int64)
         for prefix, d in (("x", self.x), ("m", self.m), ("v", self.v)):
             for k, t in d.items():
                 out[f"{prefix}.{k}"] = t.clone()
@@ -198,9 +396,13 @@ class ServerOptimizer:
         x, m, v = OrderedDict(), OrderedDict(), OrderedDict()
         dest = {"x": x, "m": m, "v": v}
         skipped = 0
+        dp_rounds = 0
         for k, t in sd.items():
             if k == "skipped_rounds":
                 skipped = int(t.item())
+                continue
+            if k == "dp_rounds":
+                dp_rounds = int(t.item())
                 continue
             prefix, _, key = k.partition(".")
             if prefix not in dest or not key:
@@ -210,6 +412,7 @@ class ServerOptimizer:
             dest[prefix][key] = t.detach().to("cpu").clone()
         self.x, self.m, self.v = x, m, v
         self.skipped_rounds = skipped
+        self.dp_rounds = dp_rounds
 
     # -- the round ---------------------------------------------------------------
 
@@ -238,6 +441,13 @@ class ServerOptimizer:
                 if k not in sd:
                     raise KeyError(f"client state_dict missing key {k!r}")
 
+        noisy = self.noise_multiplier > 0
+        if noisy:
+            t = self.dp_rounds
+            self.dp_rounds += 1          # every call, skipped rounds included
+            self.last_sigma = dp_sigma(
+                self.noise_multiplier, self.client_clip_norm,
+                max(f32(float(n_i) / total) for n_i in weights))
         self.norm, self.coef, self.finite = [], [], []
         D = {k: torch.zeros_like(self.x[k]) for k in fkeys}
         W = _t(0.0)
@@ -262,11 +472,17 @@ class ServerOptimizer:
         inv_w, self.applied = inv_weight(self.last_W)
         self.last_D, self.last_inv_W = D, inv_w
         if self.applied:
-            for k in fkeys:
+            for s, k in enumerate(fkeys):
                 mode = self.name if k in params else MEAN
-                server_update_(mode, D[k], inv_w, self.x[k], self.m.get(k),
-                               self.v.get(k), self.lr, self.beta1, self.beta2,
-                               self.tau)
+                if noisy:
+                    xi = dp_xi(self.seed, t, s, 0, D[k].numel(),
+                               self.last_sigma).reshape(D[k].shape)
+                    delta = D[k] + xi
+                else:
+                    delta = D[k] * _t(inv_w)
+                server_apply_(mode, delta, self.x[k], self.m.get(k),
+                              self.v.get(k), self.lr, self.beta1, self.beta2,
+                              self.tau)
         else:
             self.skipped_rounds += 1
 

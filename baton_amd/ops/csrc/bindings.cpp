@@ -438,11 +438,33 @@ void fedopt_finalize(at::Tensor w_sum, at::Tensor round_state) {
                          round_state.data_ptr<float>(), stream());
 }
 
-void server_step(const std::string& mode, at::Tensor D, at::Tensor x,
-                 c10::optional<at::Tensor> m, c10::optional<at::Tensor> v,
-                 double lr, double beta1, double beta2, double tau,
-                 at::Tensor round_state) {
-  const char* op = "server_step";
+namespace {
+
+// The noise arguments of server_step_noise and dp_noise, refused by name.
+struct DpNoiseArgs {
+  unsigned long long seed;
+  long long round, stream, elem_offset;
+  double sigma;
+};
+
+void dp_noise_check(const DpNoiseArgs& nz, const char* op) {
+  TORCH_CHECK(nz.round >= 0, op, ": round must be >= 0, got ", nz.round);
+  TORCH_CHECK(nz.stream >= 0 && nz.stream <= 0xFFFFFFFFll, op,
+              ": stream must be in [0, 2^32), got ", nz.stream);
+  TORCH_CHECK(nz.elem_offset >= 0 && nz.elem_offset % 4 == 0, op,
+              ": elem_offset must be a non-negative multiple of 4, got ",
+              nz.elem_offset);
+  TORCH_CHECK(std::isfinite(nz.sigma) && nz.sigma >= 0.0, op,
+              ": sigma must be finite and >= 0, got ", nz.sigma);
+}
+
+// server_step and server_step_noise: one set of refusals, then the launch
+// of NOISE = (nz != nullptr).
+void server_step_impl(const char* op, const std::string& mode, at::Tensor D,
+                      at::Tensor x, c10::optional<at::Tensor> m,
+                      c10::optional<at::Tensor> v, double lr, double beta1,
+                      double beta2, double tau, at::Tensor round_state,
+                      const DpNoiseArgs* nz) {
   const int md = server_mode(mode);
   const bool has_m = md >= 1, has_v = md >= 2;
   fedopt_check(x, "x", op);
@@ -469,9 +491,54 @@ void server_step(const std::string& mode, at::Tensor D, at::Tensor x,
   TORCH_CHECK(tau == tau, op, ": tau must not be NaN");
   TORCH_CHECK(!has_v || tau > 0.0, op,
               ": tau must be > 0 for an adaptive mode, got ", tau);
-  launch_server_step(md, D.data_ptr<float>(), x.data_ptr<float>(), mp, vp,
-                     x.numel(), (float)lr, (float)beta1, (float)beta2,
-                     (float)tau, round_state.data_ptr<float>(), stream());
+  if (nz == nullptr) {
+    launch_server_step(md, D.data_ptr<float>(), x.data_ptr<float>(), mp, vp,
+                       x.numel(), (float)lr, (float)beta1, (float)beta2,
+                       (float)tau, round_state.data_ptr<float>(), stream());
+    return;
+  }
+  dp_noise_check(*nz, op);
+  launch_server_step_noise(
+      md, D.data_ptr<float>(), x.data_ptr<float>(), mp, vp, x.numel(),
+      (float)lr, (float)beta1, (float)beta2, (float)tau,
+      round_state.data_ptr<float>(), nz->seed,
+      (unsigned)(nz->round & 0xFFFFFFFFll), (unsigned)nz->stream,
+      nz->elem_offset, (float)nz->sigma, stream());
+}
+
+}  // namespace
+
+void server_step(const std::string& mode, at::Tensor D, at::Tensor x,
+                 c10::optional<at::Tensor> m, c10::optional<at::Tensor> v,
+                 double lr, double beta1, double beta2, double tau,
+                 at::Tensor round_state) {
+  server_step_impl("server_step", mode, D, x, m, v, lr, beta1, beta2, tau,
+                   round_state, nullptr);
+}
+
+// server_step with DP-FedAvg noise (fed/server_opt.py): Delta = D + xi.
+void server_step_noise(const std::string& mode, at::Tensor D, at::Tensor x,
+                       c10::optional<at::Tensor> m,
+                       c10::optional<at::Tensor> v, double lr, double beta1,
+                       double beta2, double tau, at::Tensor round_state,
+                       unsigned long long seed, long long round,
+                       long long stream_id, long long elem_offset,
+                       double sigma) {
+  const DpNoiseArgs nz{seed, round, stream_id, elem_offset, sigma};
+  server_step_impl("server_step_noise", mode, D, x, m, v, lr, beta1, beta2,
+                   tau, round_state, &nz);
+}
+
+// out = xi alone: what server_step_noise adds to D, for tests and benchmarks.
+void dp_noise(at::Tensor out, unsigned long long seed, long long round,
+              long long stream_id, long long elem_offset, double sigma) {
+  const char* op = "dp_noise";
+  fedopt_check(out, "out", op);
+  const DpNoiseArgs nz{seed, round, stream_id, elem_offset, sigma};
+  dp_noise_check(nz, op);
+  launch_dp_noise(out.data_ptr<float>(), out.numel(), seed,
+                  (unsigned)(round & 0xFFFFFFFFll), (unsigned)stream_id,
+                  elem_offset, (float)sigma, stream());
 }
 
 at::Tensor colsum(at::Tensor x) {
@@ -1712,6 +1779,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("m"), py::arg("v"), py::arg("lr"),
         py::arg("beta1"), py::arg("beta2"), py::arg("tau"),
         py::arg("round_state"));
+  m.def("server_step_noise", &server_step_noise, py::arg("mode"),
+        py::arg("D"), py::arg("x"), py::arg("m"), py::arg("v"), py::arg("lr"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("tau"),
+        py::arg("round_state"), py::arg("seed"), py::arg("round"),
+        py::arg("stream"), py::arg("elem_offset"), py::arg("sigma"));
+  m.def("dp_noise", &dp_noise, py::arg("out"), py::arg("seed"),
+        py::arg("round"), py::arg("stream"), py::arg("elem_offset"),
+        py::arg("sigma"));
   m.def("scale_cast", &scale_cast);
   m.def("cast_copy", &cast_copy);
   m.def("axpby", &axpby);

@@ -10,6 +10,12 @@
 // Delta = D / W to x, m and v (server_step_kernel). All state is fp32, all
 // kernels use the optim.hip geometry (optim_grid blocks of 256 threads, 16 B
 // per lane, scalar tail, grid-stride), and nothing is read back by the host.
+//
+// DP-FedAvg (server_step_kernel<MODE, true>, dp_noise_kernel): Delta =
+// fl(D + xi) with xi = fl(sigma * zeta) and zeta the Philox4x32-10 unit normal
+// of (seed, round, stream, element), made in registers inside the same pass.
+// The definition (counter layout, uniforms, Box-Muller, the fixed denominator
+// and what the guarantee leaves out) is the docstring of fed/server_opt.py.
 #include "common.h"
 
 // Every operation below is rounded on its own: no a * b + c written with
@@ -128,12 +134,86 @@ enum ServerMode : int {
   kServerYogi = 4,
 };
 
-// One element of the server step: Delta = D * inv_W, then MODE's update of
-// x, m, v (no bias correction, as in the paper).
+// ---- DP noise: Philox4x32-10 and Box-Muller ----------------------------------
+
+// What a noised launch adds to the server step: the key (lo32, hi32 of the
+// seed), the round and stream words of the counter, the flat offset of
+// element 0 within the stream (a multiple of 4) and the noise scale.
+struct DpNoise {
+  unsigned key0, key1, round, stream;
+  long long elem_offset;
+  float sigma;
+};
+
+// Philox4x32-10 with the Random123 constants: ten rounds, the key bumped by
+// the Weyl increments between rounds.
+DEVINL void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
+                          unsigned k0, unsigned k1, unsigned (&r)[4]) {
+  constexpr unsigned kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u;
+  constexpr unsigned kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const unsigned hi0 = __umulhi(kM0, c0), lo0 = kM0 * c0;
+    const unsigned hi1 = __umulhi(kM1, c2), lo1 = kM1 * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += kW0;
+    k1 += kW1;
+  }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+// Two unit normals from two words: u1 in (0, 1], u2 in [0, 1), both exact.
+DEVINL void box_muller(unsigned a, unsigned b, float& z0, float& z1) {
+  const float u1 = (float)((a >> 8) + 1u) * 0x1p-24f;
+  const float u2 = (float)(b >> 8) * 0x1p-24f;
+  const float R = sqrtf(-2.f * logf(u1));
+  const float t = 2.f * u2;
+  z0 = R * cospif(t);
+  z1 = R * sinpif(t);
+}
+
+// The four unit normals of block j (elements 4 j .. 4 j + 3 of the stream).
+DEVINL void unit_normals4(const DpNoise& nz, long long j, float (&z)[4]) {
+  unsigned r[4];
+  philox4x32_10((unsigned)((unsigned long long)j & 0xFFFFFFFFull),
+                (unsigned)((unsigned long long)j >> 32), nz.round, nz.stream,
+                nz.key0, nz.key1, r);
+  box_muller(r[0], r[1], z[0], z[1]);
+  box_muller(r[2], r[3], z[2], z[3]);
+}
+
+// xi = fl(sigma * zeta) alone, on server_step_kernel's index walk: one Philox
+// call per f32x4, the tail from block (elem_offset + n) >> 2.
+__global__ void dp_noise_kernel(float* __restrict__ out, long long n,
+                                DpNoise nz) {
+  const long long nvec = n / 4;
+  const long long j0 = nz.elem_offset >> 2;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
+       i += (long long)gridDim.x * blockDim.x) {
+    float z[4];
+    unit_normals4(nz, j0 + i, z);
+    f32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = nz.sigma * z[k];
+    reinterpret_cast<f32x4*>(out)[i] = o;
+  }
+  for (long long i = nvec * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       i < n; i += (long long)gridDim.x * blockDim.x) {
+    float z[4];
+    unit_normals4(nz, j0 + nvec, z);
+    const int lane = (int)(i - nvec * 4);
+    out[i] = nz.sigma * (lane == 0 ? z[0] : lane == 1 ? z[1] : z[2]);
+  }
+}
+
+// One element of the server step from Delta: MODE's update of x, m, v (no
+// bias correction, as in the paper).
 template <int MODE>
-DEVINL void server_update(float D, float inv_w, float& x, float& m, float& v,
-                          float lr, float b1, float b2, float tau) {
-  const float delta = D * inv_w;
+DEVINL void server_update(float delta, float& x, float& m, float& v, float lr,
+                          float b1, float b2, float tau) {
   if constexpr (MODE == kServerMean) {
     x = x + delta;
   } else if constexpr (MODE == kServerAvgM) {
@@ -157,17 +237,27 @@ DEVINL void server_update(float D, float inv_w, float& x, float& m, float& v,
 
 // x, m, v updated in place from the reduced D. round_state[2] == 0 is a
 // uniform early exit: a skipped round writes nothing. Mean takes null m and
-// v, AvgM null v.
-template <int MODE>
+// v, AvgM null v. Without NOISE, Delta = fl(D * inv_W) and the pack is empty,
+// so the kernel's arguments are what they always were; with NOISE the pack is
+// one DpNoise, Delta = fl(D + fl(sigma * zeta)) and inv_W is never read.
+template <int MODE, bool NOISE, typename... Noise>
 __global__ void server_step_kernel(const float* __restrict__ D,
                                    float* __restrict__ x, float* __restrict__ m,
                                    float* __restrict__ v, long long n, float lr,
                                    float b1, float b2, float tau,
-                                   const float* __restrict__ round_state) {
+                                   const float* __restrict__ round_state,
+                                   Noise... noise) {
+  static_assert(sizeof...(Noise) == (NOISE ? 1 : 0), "one DpNoise iff NOISE");
   constexpr bool HAS_M = MODE != kServerMean;
   constexpr bool HAS_V = MODE >= kServerAdagrad;
   if (round_state[2] == 0.f) return;
-  const float inv_w = round_state[1];
+  float inv_w = 0.f;
+  DpNoise nz = {};
+  if constexpr (NOISE) {
+    nz = DpNoise{noise...};
+  } else {
+    inv_w = round_state[1];
+  }
   const long long nvec = n / 4;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
        i += (long long)gridDim.x * blockDim.x) {
@@ -176,10 +266,13 @@ __global__ void server_step_kernel(const float* __restrict__ D,
     f32x4 mv = {}, vv = {};
     if constexpr (HAS_M) mv = reinterpret_cast<const f32x4*>(m)[i];
     if constexpr (HAS_V) vv = reinterpret_cast<const f32x4*>(v)[i];
+    float z[4] = {};
+    if constexpr (NOISE) unit_normals4(nz, (nz.elem_offset >> 2) + i, z);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float xk = xv[k], mk = mv[k], vk = vv[k];
-      server_update<MODE>(dv[k], inv_w, xk, mk, vk, lr, b1, b2, tau);
+      const float delta = NOISE ? dv[k] + nz.sigma * z[k] : dv[k] * inv_w;
+      server_update<MODE>(delta, xk, mk, vk, lr, b1, b2, tau);
       xv[k] = xk; mv[k] = mk; vv[k] = vk;
     }
     reinterpret_cast<f32x4*>(x)[i] = xv;
@@ -191,7 +284,16 @@ __global__ void server_step_kernel(const float* __restrict__ D,
     float xk = x[i], mk = 0.f, vk = 0.f;
     if constexpr (HAS_M) mk = m[i];
     if constexpr (HAS_V) vk = v[i];
-    server_update<MODE>(D[i], inv_w, xk, mk, vk, lr, b1, b2, tau);
+    float delta;
+    if constexpr (NOISE) {
+      float z[4];
+      unit_normals4(nz, (nz.elem_offset >> 2) + nvec, z);
+      const int lane = (int)(i - nvec * 4);
+      delta = D[i] + nz.sigma * (lane == 0 ? z[0] : lane == 1 ? z[1] : z[2]);
+    } else {
+      delta = D[i] * inv_w;
+    }
+    server_update<MODE>(delta, xk, mk, vk, lr, b1, b2, tau);
     x[i] = xk;
     if constexpr (HAS_M) m[i] = mk;
     if constexpr (HAS_V) v[i] = vk;
@@ -238,9 +340,10 @@ void launch_server_step(int mode, const float* D, float* x, float* m, float* v,
                         long long n, float lr, float b1, float b2, float tau,
                         const float* round_state, hipStream_t s) {
   const int grid = optim_grid(n);
-#define BATON_SERVER_STEP(MODE)                                              \
-  hipLaunchKernelGGL(server_step_kernel<MODE>, dim3(grid), dim3(kBlock), 0, \
-                     s, D, x, m, v, n, lr, b1, b2, tau, round_state)
+#define BATON_SERVER_STEP(MODE)                                                \
+  hipLaunchKernelGGL((server_step_kernel<MODE, false>), dim3(grid),           \
+                     dim3(kBlock), 0, s, D, x, m, v, n, lr, b1, b2, tau,      \
+                     round_state)
   switch (mode) {
     case kServerMean: BATON_SERVER_STEP(kServerMean); break;
     case kServerAvgM: BATON_SERVER_STEP(kServerAvgM); break;
@@ -249,4 +352,41 @@ void launch_server_step(int mode, const float* D, float* x, float* m, float* v,
     default: BATON_SERVER_STEP(kServerYogi); break;
   }
 #undef BATON_SERVER_STEP
+}
+
+static DpNoise dp_noise_args(unsigned long long seed, unsigned round,
+                             unsigned stream, long long elem_offset,
+                             float sigma) {
+  return DpNoise{(unsigned)(seed & 0xFFFFFFFFull), (unsigned)(seed >> 32),
+                 round, stream, elem_offset, sigma};
+}
+
+void launch_server_step_noise(int mode, const float* D, float* x, float* m,
+                              float* v, long long n, float lr, float b1,
+                              float b2, float tau, const float* round_state,
+                              unsigned long long seed, unsigned round,
+                              unsigned stream, long long elem_offset,
+                              float sigma, hipStream_t s) {
+  const int grid = optim_grid(n);
+  const DpNoise nz = dp_noise_args(seed, round, stream, elem_offset, sigma);
+#define BATON_SERVER_STEP(MODE)                                                \
+  hipLaunchKernelGGL((server_step_kernel<MODE, true, DpNoise>), dim3(grid),   \
+                     dim3(kBlock), 0, s, D, x, m, v, n, lr, b1, b2, tau,      \
+                     round_state, nz)
+  switch (mode) {
+    case kServerMean: BATON_SERVER_STEP(kServerMean); break;
+    case kServerAvgM: BATON_SERVER_STEP(kServerAvgM); break;
+    case kServerAdagrad: BATON_SERVER_STEP(kServerAdagrad); break;
+    case kServerAdam: BATON_SERVER_STEP(kServerAdam); break;
+    default: BATON_SERVER_STEP(kServerYogi); break;
+  }
+#undef BATON_SERVER_STEP
+}
+
+void launch_dp_noise(float* out, long long n, unsigned long long seed,
+                     unsigned round, unsigned stream, long long elem_offset,
+                     float sigma, hipStream_t s) {
+  hipLaunchKernelGGL(dp_noise_kernel, dim3(optim_grid(n)), dim3(kBlock), 0, s,
+                     out, n,
+                     dp_noise_args(seed, round, stream, elem_offset, sigma));
 }

@@ -63,6 +63,19 @@ void launch_fedopt_finalize(const float* w_sum, float* round_state,
 void launch_server_step(int mode, const float* D, float* x, float* m, float* v,
                         long long n, float lr, float b1, float b2, float tau,
                         const float* round_state, hipStream_t s);
+// The same step with DP noise: Delta = fl(D + fl(sigma * zeta)), zeta the
+// Philox4x32-10 unit normal of (seed, round, stream, elem_offset + e); inv_W
+// is not read. elem_offset is a multiple of 4 (fed/server_opt.py).
+void launch_server_step_noise(int mode, const float* D, float* x, float* m,
+                              float* v, long long n, float lr, float b1,
+                              float b2, float tau, const float* round_state,
+                              unsigned long long seed, unsigned round,
+                              unsigned stream, long long elem_offset,
+                              float sigma, hipStream_t s);
+// out[e] = fl(sigma * zeta) alone, on the step's index walk.
+void launch_dp_noise(float* out, long long n, unsigned long long seed,
+                     unsigned round, unsigned stream, long long elem_offset,
+                     float sigma, hipStream_t s);
 
 // loss.hip
 void launch_mse_fwd(bool is_bf16, const void* x, const void* y, float* out,

@@ -34,7 +34,11 @@ ranks send clipped updates w_i c_i (theta_i - x) against an fp32 master x
 where FedAvg sends parameters, rank 0 applies FedAvgM / FedAdagrad / FedAdam /
 FedYogi to x between the reduce and the broadcast (ops/csrc/fedopt.hip), and
 every rank installs x. Same streams, buckets and fence; the definition and
-the CPU oracle are in fed/server_opt.py.
+the CPU oracle are in fed/server_opt.py. With `dp_noise_multiplier` > 0 rank
+0's step adds DP-FedAvg noise in the same pass (`server_step_noise` with
+rank 0's seed, the round index, the group ordinal as stream and the bucket's
+start as element offset); `dp_rounds` counts every round, skipped ones
+included, and `dp_epsilon` reports the privacy spent.
 
 CPU testing: the same class runs on gloo with world_size>1 (reduce/broadcast
 are identical calls), which is how tests/test_data_plane.py exercises the
@@ -370,8 +374,11 @@ class FederatedDataPlane:
         ServerOptConfig with a name other than 'none'."""
         from baton_amd.fed import server_opt as so
 
+        dp_z = float(getattr(cfg, "dp_noise_multiplier", 0.0))
+        dp_seed = getattr(cfg, "dp_seed", None)
+        dp_delta = float(getattr(cfg, "dp_delta", 1e-5))
         so.validate(cfg.name, cfg.lr, cfg.beta1, cfg.beta2, cfg.tau,
-                    cfg.client_clip_norm)
+                    cfg.client_clip_norm, dp_z, dp_seed, dp_delta)
         if cfg.name == "none":
             raise ValueError("enable_server_opt: server_opt.name is 'none'")
         on_gpu = self._arena_on_gpu(arena)
@@ -408,6 +415,12 @@ class FederatedDataPlane:
             clip_state=torch.zeros(4, **f32),
             w_slot=torch.zeros(1, **f32),
             round_state=torch.zeros(4, **f32),
+            # DP-FedAvg (fed/server_opt.py): off with dp_z == 0. Only rank
+            # 0's seed is ever used; dp_rounds counts every fedopt_arena call.
+            dp_z=dp_z,
+            dp_seed=so.resolve_seed(dp_seed) if dp_z > 0 else None,
+            dp_delta=dp_delta,
+            dp_rounds=0,
         )
 
     @property
@@ -424,11 +437,37 @@ class FederatedDataPlane:
         """[W, 1 / W or 0, applied 1 / 0, skipped rounds], equal on all ranks."""
         return self._fedopt["round_state"]
 
+    @property
+    def dp_enabled(self) -> bool:
+        return self._fedopt is not None and self._fedopt["dp_z"] > 0
+
+    @property
+    def dp_rounds(self) -> int:
+        """Rounds that drew noise so far (skipped rounds included)."""
+        return self._fedopt["dp_rounds"]
+
+    @property
+    def dp_delta(self) -> float:
+        return self._fedopt["dp_delta"]
+
+    @property
+    def dp_epsilon(self) -> float:
+        """eps(dp_delta) spent so far (fed.server_opt.privacy_spent)."""
+        from baton_amd.fed.server_opt import privacy_spent
+
+        st = self._fedopt
+        if st["dp_z"] <= 0:
+            return 0.0
+        return privacy_spent(st["dp_rounds"], st["dp_z"], st["dp_delta"])
+
     def server_opt_state(self) -> "dict[str, torch.Tensor]":
         """CPU copies of this rank's state: ``x.<group>`` and ``round_state``
-        everywhere, ``m.<group>`` / ``v.<group>`` on rank 0."""
+        everywhere, ``m.<group>`` / ``v.<group>`` on rank 0; with DP noise on,
+        the 0-dim int64 ``dp_rounds`` (never the seed)."""
         st = self._fedopt
         out = {"round_state": st["round_state"].detach().cpu().clone()}
+        if st["dp_z"] > 0:
+            out["dp_rounds"] = torch.tensor(st["dp_rounds"], dtype=torch.int64)
         for i, gs in enumerate(st["groups"]):
             for key in ("x", "m", "v"):
                 if gs[key] is not None:
@@ -440,6 +479,8 @@ class FederatedDataPlane:
         ``x`` and ``round_state`` are re-broadcast from rank 0, whose ``state``
         is the one that counts)."""
         st = self._fedopt
+        if st["dp_z"] > 0 and "dp_rounds" in state:
+            st["dp_rounds"] = int(state["dp_rounds"].item())
         if self.rank == 0:
             st["round_state"].copy_(state["round_state"])
         dist.broadcast(st["round_state"], src=0)
@@ -450,7 +491,8 @@ class FederatedDataPlane:
                         gs[key].copy_(state[f"{key}.{i}"])
             dist.broadcast(gs["x"], src=0)
 
-    def _fedopt_gpu_sequence(self, arena: FlatParamArena, alpha: float) -> None:
+    def _fedopt_gpu_sequence(self, arena: FlatParamArena, alpha: float,
+                             dp: Optional[tuple] = None) -> None:
         """The device side of a round, enqueued on the CALLER's current
         stream. No host read: the clip coefficient, the participation and the
         skip decision stay in clip_state / w_slot / round_state.
@@ -461,6 +503,10 @@ class FederatedDataPlane:
           4. per bucket: delta_scale_cast, async reduce; on rank 0 wait()
              on that reduce (a stream fence) and server_step on the bucket;
              async broadcast of the x bucket; then cast_copy(theta, x)
+
+        ``dp`` = (round t, sigma) turns the step into server_step_noise with
+        (seed, t, group ordinal, the bucket's lo, sigma): buckets start at
+        multiples of _BUCKET_ELEMS, so lo is a multiple of 4.
 
         Every reduce Work is kept and waited on, on every rank: nothing here
         relies on the communicator running reduce and broadcast of one
@@ -505,20 +551,27 @@ class FederatedDataPlane:
                                           async_op=True)
                 reduce_work.wait()      # stream-level fence only
                 if root:
-                    ops.server_step(
+                    step_args = (
                         gs["mode"], piece, gs["x"][lo:hi],
                         None if gs["m"] is None else gs["m"][lo:hi],
                         None if gs["v"] is None else gs["v"][lo:hi],
                         st["lr"], st["b1"], st["b2"], st["tau"], round_state)
+                    if dp is None:
+                        ops.server_step(*step_args)
+                    else:
+                        ops.server_step_noise(*step_args, st["dp_seed"],
+                                              dp[0], gi, lo, dp[1])
                 bcast_works.append(
                     dist.broadcast(gs["x"][lo:hi], src=0, async_op=True))
             for (gi, lo, hi), w in zip(buckets, bcast_works):
                 w.wait()
                 ops.cast_copy(thetas[gi][lo:hi], st["groups"][gi]["x"][lo:hi])
 
-    def _fedopt_cpu_sequence(self, arena: FlatParamArena, alpha: float) -> None:
+    def _fedopt_cpu_sequence(self, arena: FlatParamArena, alpha: float,
+                             dp: Optional[tuple] = None) -> None:
         """The same round with torch ops (gloo / CPU): the arithmetic of
-        fed.server_opt, the collectives of the device sequence."""
+        fed.server_opt, the collectives of the device sequence; with ``dp``
+        the noise is the oracle's (``dp_xi``)."""
         from baton_amd.fed import server_opt as so
 
         st = self._fedopt
@@ -544,16 +597,22 @@ class FederatedDataPlane:
             if not applied:
                 rs[3] += 1.0
         dist.broadcast(rs, src=0)
-        for theta, d, gs in zip(thetas, deltas, st["groups"]):
+        for gi, (theta, d, gs) in enumerate(zip(thetas, deltas, st["groups"])):
             if finite:
                 torch.mul(d, s, out=gs["buf"])
             else:
                 gs["buf"].zero_()      # theta's NaN never meets the 0 weight
             dist.reduce(gs["buf"], dst=0, op=dist.ReduceOp.SUM)
             if root and rs[2].item() != 0.0:
-                so.server_update_(gs["mode"], gs["buf"], rs[1].item(), gs["x"],
-                                  gs["m"], gs["v"], st["lr"], st["b1"],
-                                  st["b2"], st["tau"])
+                hp = (st["lr"], st["b1"], st["b2"], st["tau"])
+                if dp is None:
+                    so.server_update_(gs["mode"], gs["buf"], rs[1].item(),
+                                      gs["x"], gs["m"], gs["v"], *hp)
+                else:
+                    xi = so.dp_xi(st["dp_seed"], dp[0], gi, 0,
+                                  gs["buf"].numel(), dp[1])
+                    so.server_apply_(gs["mode"], gs["buf"] + xi, gs["x"],
+                                     gs["m"], gs["v"], *hp)
             dist.broadcast(gs["x"], src=0)
             theta.copy_(gs["x"].to(theta.dtype))
 
@@ -574,13 +633,20 @@ class FederatedDataPlane:
         if st is None or st["arena"] is not arena:
             raise RuntimeError(
                 "fedopt_arena: call enable_server_opt(arena, cfg) first")
-        from baton_amd.fed.server_opt import f32
+        from baton_amd.fed.server_opt import dp_sigma, f32
 
         weights = self.gather_weights(n_samples)
         total = float(weights.sum().item())
         if total <= 0:
             raise ValueError("total sample weight must be positive")
         alpha = f32(float(n_samples) / total)
+        dp = None
+        if st["dp_z"] > 0:
+            # the round index advances on every call, skipped rounds included
+            dp = (st["dp_rounds"], dp_sigma(
+                st["dp_z"], st["clip"],
+                f32(float(weights.max().item()) / total)))
+            st["dp_rounds"] += 1
         heaviest = int(torch.argmax(weights).item())
         int_bufs = [
             b for _, b in arena.model.named_buffers() if not b.is_floating_point()
@@ -592,7 +658,7 @@ class FederatedDataPlane:
             ev.record(torch.cuda.current_stream())
             with torch.cuda.stream(self._side_stream):
                 self._side_stream.wait_event(ev)
-                self._fedopt_gpu_sequence(arena, alpha)
+                self._fedopt_gpu_sequence(arena, alpha, dp)
                 for b in int_bufs:
                     dist.broadcast(b.detach(), src=heaviest)
                 done = torch.cuda.Event()
@@ -603,9 +669,9 @@ class FederatedDataPlane:
             return weights
 
         if st["on_gpu"]:
-            self._fedopt_gpu_sequence(arena, alpha)
+            self._fedopt_gpu_sequence(arena, alpha, dp)
         else:
-            self._fedopt_cpu_sequence(arena, alpha)
+            self._fedopt_cpu_sequence(arena, alpha, dp)
         for b in int_bufs:
             t = b.detach()
             if dist.get_backend() == "gloo" and t.device.type != "cpu":

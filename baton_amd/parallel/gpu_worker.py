@@ -62,6 +62,10 @@ class GPUExperimentWorker(ExperimentWorker):
         if self.plane.server_opt_enabled:
             # server optimizer over clipped updates (enable_server_opt)
             weights = self.plane.fedopt_arena(self.arena, n_samples)
+            if self.plane.rank == 0 and self.plane.dp_enabled:
+                log.info("dp: %d noised rounds, epsilon %.4g at delta %g",
+                         self.plane.dp_rounds, self.plane.dp_epsilon,
+                         self.plane.dp_delta)
         else:
             weights = self.plane.fedavg_arena(self.arena, n_samples)
         loss_history = self.plane.weighted_mean_losses(loss_history, weights)

@@ -65,6 +65,8 @@ def client_main(args) -> None:
         cfg.server_opt = ServerOptConfig(
             name=args.server_opt, lr=args.server_lr, beta1=b1, beta2=b2,
             tau=args.server_tau, client_clip_norm=args.client_clip_norm,
+            dp_noise_multiplier=args.dp_noise_multiplier,
+            dp_seed=args.dp_seed, dp_delta=args.dp_delta,
         )
         plane.enable_server_opt(arena, cfg.server_opt)
 
@@ -190,6 +192,14 @@ def main() -> None:
     p.add_argument("--server-tau", type=float, default=1e-3)
     p.add_argument("--client-clip-norm", type=float, default=0.0,
                    help="bound on each client's update norm; 0 = off")
+    p.add_argument("--dp-noise-multiplier", type=float, default=0.0,
+                   help="DP-FedAvg: Gaussian noise of std z * clip norm * "
+                        "max weight on the aggregate; needs --server-opt and "
+                        "--client-clip-norm; 0 = off")
+    p.add_argument("--dp-seed", type=int, default=None,
+                   help="64-bit seed of the noise; default: a fresh one")
+    p.add_argument("--dp-delta", type=float, default=1e-5,
+                   help="the delta of the reported epsilon")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--port", type=int, default=8080)
     p.add_argument("--dist-port", type=int, default=29531)
@@ -199,6 +209,9 @@ def main() -> None:
     p.add_argument("--done-file", default="/tmp/baton_launcher_done")
     p.add_argument("--_client", action="store_true", help=argparse.SUPPRESS)
     args = p.parse_args()
+    if args.dp_noise_multiplier != 0 and args.server_opt == "none":
+        p.error("--dp-noise-multiplier needs --server-opt and "
+                "--client-clip-norm")
 
     if args._client:
         client_main(args)

@@ -90,12 +90,18 @@ class ServerOptConfig:
     tau: float = 1e-3                # adaptivity floor; v starts at tau^2
     client_clip_norm: float = 0.0    # >0 bounds each client's update norm;
                                      # 0 = off
+    # DP-FedAvg: Gaussian noise of std z * client_clip_norm * max_i w_i on
+    # the aggregate (fed/server_opt.py). 0 = off: every path stays as it is.
+    dp_noise_multiplier: float = 0.0
+    dp_seed: Optional[int] = None    # None = a fresh 64-bit seed per process
+    dp_delta: float = 1e-5           # the delta of the reported epsilon
 
     def __post_init__(self):
         from baton_amd.fed.server_opt import validate
 
         validate(self.name, self.lr, self.beta1, self.beta2, self.tau,
-                 self.client_clip_norm)
+                 self.client_clip_norm, self.dp_noise_multiplier,
+                 self.dp_seed, self.dp_delta)
 
     @property
     def enabled(self) -> bool:

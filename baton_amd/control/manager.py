@@ -21,7 +21,10 @@ client updates, FedAvgM / FedAdagrad / FedAdam / FedYogi on an fp32 master);
 its state is a sidecar ``<name>.server_opt.ckpt`` beside the checkpoint.
 With ``server_opt.dp_noise_multiplier`` > 0 the step adds DP-FedAvg noise;
 ``dp_rounds`` and ``dp_epsilon`` appear in ``/metrics`` and ``dp_rounds`` is
-kept in the sidecar (the seed never is).
+kept in the sidecar (the seed never is). With ``server_opt.aggregator``
+'trimmed_mean' or 'median' the step combines the clients coordinate-wise;
+``robust_live`` and ``robust_trimmed`` appear in ``/metrics`` and the sidecar's
+meta names the aggregator.
 
 Checkpoint/resume: the global model is persisted per round
 with the round-start payload schema {'state_dict', 'update_name', 'n_epoch'}
@@ -297,6 +300,11 @@ class Experiment:
                 self.metrics["skipped_rounds"] = self.server_opt.skipped_rounds
                 self.metrics["last_round_W"] = self.server_opt.last_W
                 self._publish_dp_metrics()
+                if self.server_opt.aggregator != "mean":
+                    # the round's live clients k and the trim b(k) per end
+                    self.metrics["robust_live"] = self.server_opt.last_live
+                    self.metrics["robust_trimmed"] = (
+                        self.server_opt.last_trimmed)
             self.rounds.loss_history.extend(
                 weighted_loss_history(
                     [r["loss_history"] for r in responses.values()], weights
@@ -365,6 +373,7 @@ class Experiment:
         payload = encode_payload(
             {
                 "server_opt": self.server_opt.name,
+                "aggregator": self.server_opt.aggregator,
                 "round_index": self.rounds.round_index,
                 "last_round_W": self.server_opt.last_W,
             },

@@ -81,6 +81,37 @@ addressed. This is the level of the common DP training libraries in their
 default mode, not a hardened one. The seed is never written to disk or to
 metrics.
 
+Robust aggregation (Yin et al., "Byzantine-Robust Distributed Learning";
+FedMedian / FedTrimmedAvg), ``aggregator`` = "mean" (default: everything
+above, untouched), "trimmed_mean" or "median"; ``trim_fraction`` beta in
+[0, 0.5), default 0.1, is read only by "trimmed_mean". Per round:
+
+    u_i   = fl(c_i * d_i)                       unweighted: n_i does not enter
+    L     = { i : f_i = 1 },  k = |L|
+    b(k)  = floor(float64(beta) * k)            trimmed_mean (float64 product, on the host)
+          = (k - 1) // 2  (0 for k = 0)         median
+    kept  = k - 2 b(k)                          (>= 1 whenever k >= 1)
+    per element e: s_0 <= ... <= s_{k-1} = the sorted u_i[e], i in L
+    S[e]  = fl(... fl(fl(s_b + s_{b+1}) + s_{b+2}) ... + s_{k-b-1})   ascending, one rounding per add
+    Delta = fl(S * inv),  inv = float32(1 / float64(kept))
+
+Delta enters the unchanged step of each mode; float buffers take
+``x = x + Delta`` as above. A round with k = 0 is skipped exactly as a round
+with W not > 0: nothing is written and ``skipped_rounds`` goes up. Live values
+are finite by construction (a finite sum of squares implies finite elements),
+so no NaN ordering is defined. Equal values, and -0.0 and +0.0, may leave the
+sort in either order: results are defined by value, not by the sign bit of a
+zero. With at most b(k) arbitrary finite rows among the k live ones, every
+element of Delta lies within the range of the honest rows' values (up to the
+rounding of the sum). What this does not cover: integer buffers still come
+from the heaviest client, and n_i, which only that choice reads, is taken on
+trust; a client that sends a non-finite update is dropped, which lowers k and
+with it b(k). The rules are refused together with DP noise (their sensitivity
+is not C max_i w_i, so the accounting above would be wrong) and with
+``name == 'none'`` (``fedavgm`` with beta1 = 0 and lr = 1 is plain robust
+FedAvg). ``trim_table`` builds b(0 .. K) once on the host; ``robust_delta`` is
+the oracle of the device kernels (ops/csrc/fedrobust.hip).
+
 This module is the CPU oracle of that definition (``ServerOptimizer.step_``,
 what the HTTP manager runs) and holds the elementwise helpers the gloo branch
 of the data plane shares; the HIP kernels (ops/csrc/fedopt.hip) run the same
@@ -104,6 +135,8 @@ MODES = ("fedavgm", "fedadagrad", "fedadam", "fedyogi")
 ADAPTIVE = ("fedadagrad", "fedadam", "fedyogi")
 # the step of a float buffer: x = x + Delta
 MEAN = "mean"
+# how the clients' updates become one Delta
+AGGREGATORS = ("mean", "trimmed_mean", "median")
 
 
 def f32(value: float) -> float:
@@ -229,6 +262,75 @@ def dp_xi(seed: int, round: int, stream: int, offset: int, n: int,
     return _t(sigma) * zeta.float()
 
 
+# ---- robust aggregation: coordinate-wise median and trimmed mean ---------------
+
+
+def trim_table(aggregator: str, beta: float, K: int) -> List[int]:
+    """b(k) for k = 0 .. K: how many values are dropped at each end with k
+    live clients (the module docstring). beta < 0.5 keeps 2 b(k) < k: the
+    float64 product beta * k lies at least half a spacing below k / 2."""
+    if aggregator not in AGGREGATORS or aggregator == "mean":
+        raise ValueError(
+            f"trim_table: aggregator must be trimmed_mean or median, got "
+            f"{aggregator!r}")
+    K = int(K)
+    if K < 0:
+        raise ValueError(f"trim_table: K must be >= 0, got {K}")
+    if aggregator == "median":
+        return [0 if k == 0 else (k - 1) // 2 for k in range(K + 1)]
+    beta = float(beta)
+    if not 0.0 <= beta < 0.5:
+        raise ValueError(
+            f"server_opt.trim_fraction must be in [0, 0.5), got {beta}")
+    return [int(math.floor(beta * k)) for k in range(K + 1)]
+
+
+def robust_counts(flags, table: Sequence[int]):
+    """(k, b, kept, inv, applied) from the clients' flags and ``trim_table``'s
+    table: robust_finalize_kernel's rule."""
+    flags = [bool(f) for f in flags]
+    if len(table) != len(flags) + 1:
+        raise ValueError(
+            f"the trim table must have {len(flags) + 1} entries, got "
+            f"{len(table)}")
+    k = sum(flags)
+    applied = k > 0
+    b = int(table[k]) if applied else 0
+    b = min(max(b, 0), (k - 1) // 2 if applied else 0)
+    kept = k - 2 * b
+    return k, b, kept, (f32(1.0 / kept) if applied else 0.0), applied
+
+
+def robust_sum(U: torch.Tensor, flags, table: Sequence[int]) -> torch.Tensor:
+    """S: per element the ascending sequential fp32 sum of the sorted live
+    rows of ``U`` ([K, n] fp32) from rank b to rank k - b - 1. Dead rows are
+    never read. Zeros with k = 0."""
+    if U.dim() != 2 or U.dtype != torch.float32:
+        raise ValueError("robust_sum: U must be a 2-D fp32 tensor")
+    if U.shape[0] != len(flags):
+        raise ValueError("robust_sum: one flag per row of U")
+    k, b, kept, _, applied = robust_counts(flags, table)
+    S = torch.zeros(U.shape[1], dtype=torch.float32)
+    if not applied:
+        return S
+    live = [i for i, f in enumerate(flags) if bool(f)]
+    s = torch.sort(U.detach().to("cpu")[live], dim=0).values
+    S.copy_(s[b])
+    for j in range(b + 1, k - b):
+        S = S + s[j]                 # fp32, one rounding per add
+    return S
+
+
+def robust_delta(U: torch.Tensor, flags,
+                 table: Sequence[int]) -> Optional[torch.Tensor]:
+    """Delta = fl(S * inv) of the live rows of ``U``, or None for a round
+    without a live row (k = 0: the round is skipped)."""
+    _, _, _, inv, applied = robust_counts(flags, table)
+    if not applied:
+        return None
+    return robust_sum(U, flags, table) * _t(inv)
+
+
 def server_update_(mode: str, D: torch.Tensor, inv_w: float, x: torch.Tensor,
                    m: Optional[torch.Tensor], v: Optional[torch.Tensor],
                    lr: float, b1: float, b2: float, tau: float) -> None:
@@ -265,10 +367,31 @@ def server_apply_(mode: str, delta: torch.Tensor, x: torch.Tensor,
 
 def validate(name: str, lr: float, beta1: float, beta2: float, tau: float,
              client_clip_norm: float, dp_noise_multiplier: float = 0.0,
-             dp_seed: Optional[int] = None, dp_delta: float = 1e-5) -> None:
+             dp_seed: Optional[int] = None, dp_delta: float = 1e-5,
+             aggregator: str = "mean", trim_fraction: float = 0.1) -> None:
     if name != "none" and name not in MODES:
         raise ValueError(
             f"unknown server optimizer {name!r} (none, {', '.join(MODES)})")
+    if aggregator not in AGGREGATORS:
+        raise ValueError(
+            f"unknown server_opt.aggregator {aggregator!r} "
+            f"({', '.join(AGGREGATORS)})")
+    if not 0.0 <= trim_fraction < 0.5:
+        raise ValueError(
+            f"server_opt.trim_fraction must be in [0, 0.5), got "
+            f"{trim_fraction}")
+    if aggregator != "mean":
+        if name == "none":
+            raise ValueError(
+                f"server_opt.aggregator {aggregator!r} needs a server "
+                "optimizer (name is 'none'): fedavgm with beta1 = 0 and "
+                "lr = 1 is plain robust FedAvg")
+        if dp_noise_multiplier != 0:
+            raise ValueError(
+                f"server_opt.aggregator {aggregator!r} cannot be combined "
+                "with dp_noise_multiplier > 0: the sensitivity of a robust "
+                "rule is not C max_i w_i, so the privacy accounting would be "
+                "wrong")
     if not lr > 0:
         raise ValueError(f"server_opt.lr must be > 0, got {lr}")
     for label, b in (("beta1", beta1), ("beta2", beta2)):
@@ -314,14 +437,24 @@ class ServerOptimizer:
     every float tensor. ``client_clip_norm`` 0 (or inf) means no clipping.
     ``noise_multiplier`` > 0 turns DP-FedAvg on (the module docstring):
     ``seed`` None draws a fresh one, ``dp_rounds`` counts the calls of
-    ``step_`` made with it, skipped rounds included."""
+    ``step_`` made with it, skipped rounds included. ``aggregator``
+    "trimmed_mean" (with ``trim_fraction``) or "median" combines the clients
+    coordinate-wise instead; ``last_live`` and ``last_trimmed`` are then the
+    last round's k and b(k)."""
 
     def __init__(self, name: str = "fedavgm", lr: float = 1.0,
                  beta1: float = 0.9, beta2: float = 0.99, tau: float = 1e-3,
                  client_clip_norm: float = 0.0, noise_multiplier: float = 0.0,
-                 seed: Optional[int] = None, delta: float = 1e-5):
+                 seed: Optional[int] = None, delta: float = 1e-5,
+                 aggregator: str = "mean", trim_fraction: float = 0.1):
         validate(name, lr, beta1, beta2, tau, client_clip_norm,
-                 noise_multiplier, seed, delta)
+                 noise_multiplier, seed, delta, aggregator, trim_fraction)
+        # "mean", or a robust rule (the module docstring): then the last
+        # round's live clients k and trim b(k) are last_live, last_trimmed
+        self.aggregator = aggregator
+        self.trim_fraction = float(trim_fraction)
+        self.last_live = 0
+        self.last_trimmed = 0
         self.noise_multiplier = float(noise_multiplier)
         self.delta = float(delta)
         self.seed = resolve_seed(seed) if self.noise_multiplier > 0 else None
@@ -355,7 +488,8 @@ class ServerOptimizer:
             return None
         return cls(cfg.name, cfg.lr, cfg.beta1, cfg.beta2, cfg.tau,
                    cfg.client_clip_norm, cfg.dp_noise_multiplier, cfg.dp_seed,
-                   cfg.dp_delta)
+                   cfg.dp_delta, getattr(cfg, "aggregator", "mean"),
+                   getattr(cfg, "trim_fraction", 0.1))
 
     @property
     def epsilon(self) -> float:
@@ -441,6 +575,10 @@ class ServerOptimizer:
                 if k not in sd:
                     raise KeyError(f"client state_dict missing key {k!r}")
 
+        if self.aggregator != "mean":
+            self._robust_round(client_sds, fkeys, params)
+            return self._install(global_sd, client_sds, weights)
+
         noisy = self.noise_multiplier > 0
         if noisy:
             t = self.dp_rounds
@@ -485,7 +623,48 @@ class ServerOptimizer:
                               self.tau)
         else:
             self.skipped_rounds += 1
+        return self._install(global_sd, client_sds, weights)
 
+    def _robust_round(self, client_sds, fkeys: List[str], params) -> None:
+        """The round of a robust aggregator on x, m, v: the clients' clipped,
+        unweighted updates u_i = c_i d_i, per key the kept sum over the
+        sorted live clients, Delta = S / kept into the unchanged step."""
+        self.norm, self.coef, self.finite = [], [], []
+        rows: Dict[str, List[torch.Tensor]] = {k: [] for k in fkeys}
+        for sd in client_sds:
+            deltas = {
+                k: sd[k].detach().to("cpu", torch.float32) - self.x[k]
+                for k in fkeys
+            }
+            sumsq = sum(float(d.double().pow(2).sum()) for d in deltas.values())
+            norm, coef, finite = clip_coef(sumsq, self.client_clip_norm)
+            self.norm.append(norm)
+            self.coef.append(coef)
+            self.finite.append(finite)
+            for k in fkeys:
+                # a dead client's row is never read: zeros stand in for it
+                rows[k].append((_t(coef) * deltas[k]).reshape(-1) if finite
+                               else torch.zeros(deltas[k].numel()))
+        table = trim_table(self.aggregator, self.trim_fraction,
+                           len(client_sds))
+        k_live, b, kept, inv, self.applied = robust_counts(self.finite, table)
+        self.last_live, self.last_trimmed = k_live, b
+        self.last_W, self.last_inv_W = float(kept), inv
+        self.last_D = {}
+        if not self.applied:
+            self.skipped_rounds += 1
+            return
+        for k in fkeys:
+            S = robust_sum(torch.stack(rows[k]), self.finite, table)
+            self.last_D[k] = S.reshape(self.x[k].shape)
+            mode = self.name if k in params else MEAN
+            server_apply_(mode, self.last_D[k] * _t(inv), self.x[k],
+                          self.m.get(k), self.v.get(k), self.lr, self.beta1,
+                          self.beta2, self.tau)
+
+    def _install(self, global_sd, client_sds, weights):
+        """x into ``global_sd`` in its dtypes; integer buffers from the
+        heaviest client."""
         heaviest = max(range(len(weights)), key=lambda i: weights[i])
         for k, gt in global_sd.items():
             if gt.is_floating_point():

@@ -541,6 +541,75 @@ void dp_noise(at::Tensor out, unsigned long long seed, long long round,
                   elem_offset, (float)sigma, stream());
 }
 
+// ---- robust aggregation (fedrobust.hip) ---------------------------------------
+
+namespace {
+
+// K of a robust op from flags: 1 .. 16 rows.
+long long robust_rows(const at::Tensor& flags, const char* op) {
+  const long long K = flags.numel();
+  TORCH_CHECK(K >= 1 && K <= 16, op, ": flags must have 1 to 16 elements (one "
+              "per client row), got ", K);
+  return K;
+}
+
+}  // namespace
+
+// flags[K] and b_table[K + 1] -> round_state, agg_state = [k, b].
+void robust_finalize(at::Tensor flags, at::Tensor b_table,
+                     at::Tensor round_state, at::Tensor agg_state) {
+  const char* op = "robust_finalize";
+  fedopt_check(flags, "flags", op);
+  const long long K = robust_rows(flags, op);
+  TORCH_CHECK(b_table.defined() && b_table.is_cuda() &&
+                  b_table.device() == flags.device(),
+              op, ": b_table must be on the device of the other tensors");
+  TORCH_CHECK(b_table.scalar_type() == at::kInt, op,
+              ": b_table must be int32");
+  TORCH_CHECK(b_table.is_contiguous(), op, ": b_table must be contiguous");
+  TORCH_CHECK(b_table.numel() == K + 1, op, ": b_table must have ", K + 1,
+              " elements (one per k = 0 .. K), got ", b_table.numel());
+  fedopt_check(round_state, "round_state", op, flags.device(), 4);
+  fedopt_check(agg_state, "agg_state", op, flags.device(), 2);
+  launch_robust_finalize(flags.data_ptr<float>(), b_table.data_ptr<int>(),
+                         (int)K, round_state.data_ptr<float>(),
+                         agg_state.data_ptr<float>(), stream());
+}
+
+// D = the kept sum of the rows of U (2-D fp32, unit inner stride).
+void robust_select(at::Tensor D, at::Tensor U, at::Tensor flags,
+                   at::Tensor agg_state, at::Tensor round_state) {
+  const char* op = "robust_select";
+  fedopt_check(D, "D", op);
+  TORCH_CHECK(U.defined(), op, ": U is undefined");
+  TORCH_CHECK(U.is_cuda() && U.device() == D.device(), op,
+              ": U must be on the device of the other tensors");
+  TORCH_CHECK(U.scalar_type() == at::kFloat, op, ": U must be fp32");
+  TORCH_CHECK(U.dim() == 2, op, ": U must be 2-D (K rows of n), got ", U.dim(),
+              " dimensions");
+  const long long K = U.size(0), n = U.size(1);
+  TORCH_CHECK(K >= 1 && K <= 16, op, ": U must have 1 to 16 rows, got ", K);
+  TORCH_CHECK(n == D.numel(), op, ": U's rows must have D's ", D.numel(),
+              " elements, got ", n);
+  TORCH_CHECK(n <= 1 || U.stride(1) == 1, op,
+              ": U must have unit inner stride, got ", U.stride(1));
+  const long long stride = K > 1 ? U.stride(0) : 0;
+  TORCH_CHECK(stride >= 0 && (K == 1 || stride >= n), op,
+              ": U's row stride ", stride, " is smaller than its row length ",
+              n);
+  TORCH_CHECK(stride % 4 == 0, op, ": U's row stride must be a multiple of 4 "
+              "elements (16 bytes), got ", stride);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(U.data_ptr()) % 16 == 0, op,
+              ": U must be 16-byte aligned");
+  fedopt_check(flags, "flags", op, D.device(), K);
+  fedopt_check(agg_state, "agg_state", op, D.device(), 2);
+  fedopt_check(round_state, "round_state", op, D.device(), 4);
+  launch_robust_select((int)K, D.data_ptr<float>(), U.data_ptr<float>(),
+                       stride, n, flags.data_ptr<float>(),
+                       agg_state.data_ptr<float>(),
+                       round_state.data_ptr<float>(), stream());
+}
+
 at::Tensor colsum(at::Tensor x) {
   check_first(x, "x", "colsum");
   const NormShape sh = norm_shape(x, "colsum", false);
@@ -1787,6 +1856,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dp_noise", &dp_noise, py::arg("out"), py::arg("seed"),
         py::arg("round"), py::arg("stream"), py::arg("elem_offset"),
         py::arg("sigma"));
+  m.def("robust_finalize", &robust_finalize, py::arg("flags"),
+        py::arg("b_table"), py::arg("round_state"), py::arg("agg_state"));
+  m.def("robust_select", &robust_select, py::arg("D"), py::arg("U"),
+        py::arg("flags"), py::arg("agg_state"), py::arg("round_state"));
   m.def("scale_cast", &scale_cast);
   m.def("cast_copy", &cast_copy);
   m.def("axpby", &axpby);

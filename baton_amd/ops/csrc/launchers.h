@@ -77,6 +77,22 @@ void launch_dp_noise(float* out, long long n, unsigned long long seed,
                      unsigned round, unsigned stream, long long elem_offset,
                      float sigma, hipStream_t s);
 
+// fedrobust.hip — coordinate-wise median and trimmed mean in front of the
+// server step. flags (fp32, live iff != 0), round_state[4] and agg_state[2]
+// are fp32, b_table is int32 with K + 1 entries.
+// round_state = [kept, 1 / kept or 0, applied 1 / 0, skipped rounds] and
+// agg_state = [k live rows, b = b_table[k]] from flags[0 .. K).
+void launch_robust_finalize(const float* flags, const int* b_table, int K,
+                            float* round_state, float* agg_state,
+                            hipStream_t s);
+// D[e] = the ascending sequential sum of the sorted live U[0 .. K)[e] from
+// rank b to rank k - b - 1; K in 1 .. 16, rows `stride` elements apart (a
+// multiple of 4). Nothing is written when round_state[2] == 0.
+void launch_robust_select(int K, float* D, const float* U, long long stride,
+                          long long n, const float* flags,
+                          const float* agg_state, const float* round_state,
+                          hipStream_t s);
+
 // loss.hip
 void launch_mse_fwd(bool is_bf16, const void* x, const void* y, float* out,
                     long long n, hipStream_t s);

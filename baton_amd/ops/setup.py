@@ -21,6 +21,7 @@ SRC = [
         "optim.hip",
         "fedmath.hip",
         "fedopt.hip",
+        "fedrobust.hip",
         "loss.hip",
         "norm.hip",
         "elementwise.hip",

@@ -38,7 +38,11 @@ the CPU oracle are in fed/server_opt.py. With `dp_noise_multiplier` > 0 rank
 0's step adds DP-FedAvg noise in the same pass (`server_step_noise` with
 rank 0's seed, the round index, the group ordinal as stream and the bucket's
 start as element offset); `dp_rounds` counts every round, skipped ones
-included, and `dp_epsilon` reports the privacy spent.
+included, and `dp_epsilon` reports the privacy spent. With `aggregator`
+'trimmed_mean' or 'median' the ranks send unweighted clipped updates, rank 0
+gathers them bucket by bucket into staging rows and `robust_select`
+(ops/csrc/fedrobust.hip) writes their coordinate-wise kept sum where the
+reduce would have left D; the step, the broadcast and the cast are the same.
 
 CPU testing: the same class runs on gloo with world_size>1 (reduce/broadcast
 are identical calls), which is how tests/test_data_plane.py exercises the
@@ -371,19 +375,52 @@ class FederatedDataPlane:
         once: ``partials``, ``clip_state``, ``w_slot``, ``round_state``.
         ``x`` is initialised from the arena and broadcast from rank 0, so
         all ranks start equal. Nothing is allocated per round. ``cfg`` is a
-        ServerOptConfig with a name other than 'none'."""
+        ServerOptConfig with a name other than 'none'.
+
+        With ``cfg.aggregator`` 'trimmed_mean' or 'median' (K = world size):
+        ``flags`` [K], ``agg_state`` [k, b] and the int32 ``b_table`` [K + 1]
+        on every rank, and on the GPU path, on rank 0 only, two fp32 staging
+        buffers of K rows of one bucket (at most ``_BUCKET_ELEMS`` elements)
+        that the clients' pieces are gathered into: 16 MiB per row, so 256 MB
+        each at K = 16. World sizes above 16 are refused on the GPU path."""
         from baton_amd.fed import server_opt as so
 
         dp_z = float(getattr(cfg, "dp_noise_multiplier", 0.0))
         dp_seed = getattr(cfg, "dp_seed", None)
         dp_delta = float(getattr(cfg, "dp_delta", 1e-5))
+        agg = getattr(cfg, "aggregator", "mean")
+        beta = float(getattr(cfg, "trim_fraction", 0.1))
         so.validate(cfg.name, cfg.lr, cfg.beta1, cfg.beta2, cfg.tau,
-                    cfg.client_clip_norm, dp_z, dp_seed, dp_delta)
+                    cfg.client_clip_norm, dp_z, dp_seed, dp_delta, agg, beta)
         if cfg.name == "none":
             raise ValueError("enable_server_opt: server_opt.name is 'none'")
         on_gpu = self._arena_on_gpu(arena)
         dev = self.device if on_gpu else torch.device("cpu")
         f32 = dict(dtype=torch.float32, device=dev)
+        robust = None
+        if agg != "mean":
+            K = self.world_size
+            if on_gpu and K > 16:
+                raise ValueError(
+                    f"enable_server_opt: aggregator {agg!r} supports at most "
+                    f"16 ranks on the device, got {K}")
+            table = so.trim_table(agg, beta, K)
+            if table[K] == 0 and self.rank == 0:
+                log.warning(
+                    "aggregator %s trims nothing at world size %d (b = 0): "
+                    "it is the unweighted mean of the clipped updates", agg, K)
+            stage = None
+            if on_gpu and self.rank == 0:
+                width = min(_BUCKET_ELEMS, max(
+                    (g.flat.numel() + 3) // 4 * 4 for g in arena.all_groups))
+                stage = [torch.empty((K, width), **f32) for _ in range(2)]
+            robust = dict(
+                aggregator=agg, table=table,
+                flags=torch.zeros(K, **f32),
+                agg_state=torch.zeros(2, **f32),
+                b_table=torch.tensor(table, dtype=torch.int32, device=dev),
+                stage=stage,
+            )
         groups = []
         n_blocks = 0
         for i, g in enumerate(arena.all_groups):
@@ -421,6 +458,8 @@ class FederatedDataPlane:
             dp_seed=so.resolve_seed(dp_seed) if dp_z > 0 else None,
             dp_delta=dp_delta,
             dp_rounds=0,
+            # median / trimmed mean (fed/server_opt.py): None with 'mean'
+            robust=robust,
         )
 
     @property
@@ -436,6 +475,13 @@ class FederatedDataPlane:
     def fedopt_round_state(self) -> torch.Tensor:
         """[W, 1 / W or 0, applied 1 / 0, skipped rounds], equal on all ranks."""
         return self._fedopt["round_state"]
+
+    @property
+    def fedopt_agg_state(self) -> Optional[torch.Tensor]:
+        """[k live clients, b trimmed per end] of the last round on rank 0;
+        None with the 'mean' aggregator."""
+        robust = self._fedopt["robust"]
+        return None if robust is None else robust["agg_state"]
 
     @property
     def dp_enabled(self) -> bool:
@@ -616,6 +662,157 @@ class FederatedDataPlane:
             dist.broadcast(gs["x"], src=0)
             theta.copy_(gs["x"].to(theta.dtype))
 
+    def _robust_gpu_sequence(self, arena: FlatParamArena) -> None:
+        """The device side of a round under 'trimmed_mean' or 'median', on
+        the CALLER's current stream, without a host read:
+
+          1. delta_sumsq per group, one clip_finalize (as the mean round)
+          2. delta_scale_cast of the first bucket with alpha = 1.0: the
+             piece is u_i = c_i d_i and w_slot the flag f_i
+          3. gather w_slot into flags on rank 0, robust_finalize there,
+             broadcast round_state
+          4. per bucket: delta_scale_cast, async gather of the pieces into
+             the rows of a staging buffer on rank 0, one bucket ahead of the
+             step and alternating the two buffers
+          5. on rank 0 wait() on that gather, robust_select of the staging
+             rows into the reduce buffer's bucket, server_step on it
+          6. async broadcast of the x bucket; then cast_copy(theta, x)
+
+        Every gather and broadcast Work is kept and waited on, on every
+        rank. A gather into a staging buffer is issued after the select that
+        last read that buffer was enqueued, and collectives start behind the
+        work already on the issuing stream."""
+        from baton_amd.ops._ext import require_hip
+
+        ops = require_hip()
+        st = self._fedopt
+        rb = st["robust"]
+        root = self.rank == 0
+        K = self.world_size
+        clip_state, w_slot, round_state = (
+            st["clip_state"], st["w_slot"], st["round_state"])
+        flags, agg_state = rb["flags"], rb["agg_state"]
+        thetas = [g.flat.detach().reshape(-1) for g in arena.all_groups]
+        with trace_scope("fedopt_norm"):
+            off = 0
+            for theta, gs in zip(thetas, st["groups"]):
+                off += ops.delta_sumsq(theta, gs["x"], st["partials"], off)
+            ops.clip_finalize(st["partials"], off, st["clip"], clip_state)
+        buckets = [
+            (gi, lo, min(lo + _BUCKET_ELEMS, theta.numel()))
+            for gi, theta in enumerate(thetas)
+            for lo in range(0, theta.numel(), _BUCKET_ELEMS)
+        ]
+
+        def cast_and_gather(k: int, w_out):
+            gi, lo, hi = buckets[k]
+            gs = st["groups"][gi]
+            piece = gs["buf"][lo:hi]
+            ops.delta_scale_cast(piece, thetas[gi][lo:hi], gs["x"][lo:hi],
+                                 1.0, clip_state, w_out)
+            if w_out is not None:
+                dist.gather(
+                    w_slot, [flags[r:r + 1] for r in range(K)] if root
+                    else None, dst=0, async_op=True).wait()
+                if root:
+                    ops.robust_finalize(flags, rb["b_table"], round_state,
+                                        agg_state)
+                dist.broadcast(round_state, src=0, async_op=True).wait()
+            rows = None
+            if root:
+                stage = rb["stage"][k % 2]
+                rows = [stage[r, :hi - lo] for r in range(K)]
+            return dist.gather(piece, rows, dst=0, async_op=True)
+
+        with trace_scope("fedopt_gather_select_step_bcast"):
+            gather_work = cast_and_gather(0, w_slot)
+            bcast_works = []
+            for k, (gi, lo, hi) in enumerate(buckets):
+                next_work = (cast_and_gather(k + 1, None)
+                             if k + 1 < len(buckets) else None)
+                gather_work.wait()      # stream-level fence only
+                gs = st["groups"][gi]
+                if root:
+                    piece = gs["buf"][lo:hi]
+                    ops.robust_select(piece, rb["stage"][k % 2][:, :hi - lo],
+                                      flags, agg_state, round_state)
+                    ops.server_step(
+                        gs["mode"], piece, gs["x"][lo:hi],
+                        None if gs["m"] is None else gs["m"][lo:hi],
+                        None if gs["v"] is None else gs["v"][lo:hi],
+                        st["lr"], st["b1"], st["b2"], st["tau"], round_state)
+                bcast_works.append(
+                    dist.broadcast(gs["x"][lo:hi], src=0, async_op=True))
+                gather_work = next_work
+            for (gi, lo, hi), w in zip(buckets, bcast_works):
+                w.wait()
+                ops.cast_copy(thetas[gi][lo:hi], st["groups"][gi]["x"][lo:hi])
+
+    def _robust_cpu_sequence(self, arena: FlatParamArena) -> None:
+        """The same round with torch ops (gloo / CPU): the collectives of the
+        device sequence, the oracle helpers of fed.server_opt."""
+        from baton_amd.fed import server_opt as so
+
+        st = self._fedopt
+        rb = st["robust"]
+        root = self.rank == 0
+        K = self.world_size
+        cpu32 = dict(device="cpu", dtype=torch.float32)
+        thetas = [g.flat.detach().reshape(-1) for g in arena.all_groups]
+        deltas = [t.to(**cpu32) - gs["x"] for t, gs in zip(thetas, st["groups"])]
+        sumsq = sum(float(d.double().pow(2).sum()) for d in deltas)
+        norm, coef, finite = so.clip_coef(sumsq, st["clip"])
+        cs = st["clip_state"]
+        cs[0], cs[1], cs[2] = norm, coef, float(finite)
+        if not finite:
+            cs[3] += 1.0
+        s = torch.tensor(1.0, dtype=torch.float32) * torch.tensor(
+            coef, dtype=torch.float32)
+        st["w_slot"][0] = 1.0 if finite else 0.0
+        flags = rb["flags"]
+        dist.gather(st["w_slot"],
+                    [flags[r:r + 1] for r in range(K)] if root else None,
+                    dst=0)
+        rs = st["round_state"]
+        live: list = []
+        if root:
+            live = [f != 0.0 for f in flags.tolist()]
+            k, b, kept, inv, applied = so.robust_counts(live, rb["table"])
+            rs[0], rs[1], rs[2] = float(kept), inv, float(applied)
+            if not applied:
+                rs[3] += 1.0
+            rb["agg_state"][0], rb["agg_state"][1] = float(k), float(b)
+        dist.broadcast(rs, src=0)
+        for theta, d, gs in zip(thetas, deltas, st["groups"]):
+            if finite:
+                torch.mul(d, s, out=gs["buf"])
+            else:
+                gs["buf"].zero_()      # a dead row: gathered, never read
+            rows = ([torch.empty_like(gs["buf"]) for _ in range(K)]
+                    if root else None)
+            dist.gather(gs["buf"], rows, dst=0)
+            if root and rs[2].item() != 0.0:
+                S = so.robust_sum(torch.stack(rows), live, rb["table"])
+                so.server_update_(gs["mode"], S, rs[1].item(), gs["x"],
+                                  gs["m"], gs["v"], st["lr"], st["b1"],
+                                  st["b2"], st["tau"])
+            dist.broadcast(gs["x"], src=0)
+            theta.copy_(gs["x"].to(theta.dtype))
+
+    def _fedopt_sequence(self, arena: FlatParamArena, alpha: float,
+                         dp: Optional[tuple]) -> None:
+        """The round's sequence for this plane's aggregator and device."""
+        st = self._fedopt
+        if st["robust"] is not None:
+            if st["on_gpu"]:
+                self._robust_gpu_sequence(arena)
+            else:
+                self._robust_cpu_sequence(arena)
+        elif st["on_gpu"]:
+            self._fedopt_gpu_sequence(arena, alpha, dp)
+        else:
+            self._fedopt_cpu_sequence(arena, alpha, dp)
+
     def fedopt_arena(
         self, arena: FlatParamArena, n_samples: int, async_handle: bool = False
     ) -> torch.Tensor:
@@ -628,7 +825,10 @@ class FederatedDataPlane:
         were and still resets every rank to x. Integer buffers come from the
         heaviest client. The stream, side-stream and ``PendingAggregation``
         protocol is ``fedavg_arena``'s; the returned value is the weight
-        vector."""
+        vector. Under 'trimmed_mean' or 'median' the ranks send the unweighted
+        ``c_i (theta_i - x)``, rank 0 gathers them and steps ``x`` with their
+        coordinate-wise kept mean; ``n_samples`` then only picks the rank the
+        integer buffers come from."""
         st = self._fedopt
         if st is None or st["arena"] is not arena:
             raise RuntimeError(
@@ -658,7 +858,7 @@ class FederatedDataPlane:
             ev.record(torch.cuda.current_stream())
             with torch.cuda.stream(self._side_stream):
                 self._side_stream.wait_event(ev)
-                self._fedopt_gpu_sequence(arena, alpha, dp)
+                self._fedopt_sequence(arena, alpha, dp)
                 for b in int_bufs:
                     dist.broadcast(b.detach(), src=heaviest)
                 done = torch.cuda.Event()
@@ -668,10 +868,7 @@ class FederatedDataPlane:
                 self.pending.wait()
             return weights
 
-        if st["on_gpu"]:
-            self._fedopt_gpu_sequence(arena, alpha, dp)
-        else:
-            self._fedopt_cpu_sequence(arena, alpha, dp)
+        self._fedopt_sequence(arena, alpha, dp)
         for b in int_bufs:
             t = b.detach()
             if dist.get_backend() == "gloo" and t.device.type != "cpu":

@@ -67,6 +67,7 @@ def client_main(args) -> None:
             tau=args.server_tau, client_clip_norm=args.client_clip_norm,
             dp_noise_multiplier=args.dp_noise_multiplier,
             dp_seed=args.dp_seed, dp_delta=args.dp_delta,
+            aggregator=args.aggregator, trim_fraction=args.trim_fraction,
         )
         plane.enable_server_opt(arena, cfg.server_opt)
 
@@ -200,6 +201,15 @@ def main() -> None:
                    help="64-bit seed of the noise; default: a fresh one")
     p.add_argument("--dp-delta", type=float, default=1e-5,
                    help="the delta of the reported epsilon")
+    p.add_argument("--aggregator", default="mean",
+                   choices=["mean", "trimmed_mean", "median"],
+                   help="how the clients' clipped updates are combined: the "
+                        "weighted mean, or coordinate-wise trimmed mean / "
+                        "median (needs --server-opt, at most 16 clients, no "
+                        "DP noise)")
+    p.add_argument("--trim-fraction", type=float, default=0.1,
+                   help="trimmed_mean drops floor(fraction * live clients) "
+                        "values at each end; in [0, 0.5)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--port", type=int, default=8080)
     p.add_argument("--dist-port", type=int, default=29531)
@@ -212,6 +222,19 @@ def main() -> None:
     if args.dp_noise_multiplier != 0 and args.server_opt == "none":
         p.error("--dp-noise-multiplier needs --server-opt and "
                 "--client-clip-norm")
+    if not 0.0 <= args.trim_fraction < 0.5:
+        p.error("--trim-fraction must be in [0, 0.5)")
+    if args.aggregator != "mean":
+        if args.server_opt == "none":
+            p.error(f"--aggregator {args.aggregator} needs --server-opt "
+                    "(fedavgm with --server-betas 0 0.99 and --server-lr 1 "
+                    "is plain robust FedAvg)")
+        if args.dp_noise_multiplier != 0:
+            p.error(f"--aggregator {args.aggregator} cannot be combined with "
+                    "--dp-noise-multiplier")
+        if args.clients > 16:
+            p.error(f"--aggregator {args.aggregator} supports at most 16 "
+                    "clients")
 
     if args._client:
         client_main(args)

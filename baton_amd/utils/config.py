@@ -95,13 +95,19 @@ class ServerOptConfig:
     dp_noise_multiplier: float = 0.0
     dp_seed: Optional[int] = None    # None = a fresh 64-bit seed per process
     dp_delta: float = 1e-5           # the delta of the reported epsilon
+    # How the clients' updates become one Delta: 'mean' (the weighted sum, the
+    # code path without any of this) | 'trimmed_mean' | 'median', coordinate-
+    # wise over the clipped, unweighted updates (fed/server_opt.py).
+    aggregator: str = "mean"
+    trim_fraction: float = 0.1       # beta of 'trimmed_mean', in [0, 0.5)
 
     def __post_init__(self):
         from baton_amd.fed.server_opt import validate
 
         validate(self.name, self.lr, self.beta1, self.beta2, self.tau,
                  self.client_clip_norm, self.dp_noise_multiplier,
-                 self.dp_seed, self.dp_delta)
+                 self.dp_seed, self.dp_delta, self.aggregator,
+                 self.trim_fraction)
 
     @property
     def enabled(self) -> bool:

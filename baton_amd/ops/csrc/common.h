@@ -96,17 +96,37 @@ DEVINL void vstore16(T* p, const float* f) {
   *reinterpret_cast<typename VT::VecT*>(p) = v;
 }
 
-// Width-generic forms: W == VecTraits<T>::kElems is the 16-B vector, W == 1
-// one element.
+// Width-generic forms: W == 1 moves one element, any multiple of
+// VecTraits<T>::kElems moves W / kElems 16-B vectors (the fp32 side buffers of
+// a bf16 kernel: 8 lanes are two f32x4).
 template <int W, typename T>
 DEVINL void vload(const T* p, float* f) {
-  if constexpr (W == 1) f[0] = (float)p[0];
-  else vload16(p, f);
+  if constexpr (W == 1) {
+    f[0] = (float)p[0];
+  } else {
+    constexpr int E = VecTraits<T>::kElems;
+    static_assert(W % E == 0, "W is 1 or whole 16-B vectors");
+#pragma unroll
+    for (int q = 0; q < W / E; ++q) vload16(p + q * E, f + q * E);
+  }
 }
 template <int W, typename T>
 DEVINL void vstore(T* p, const float* f) {
-  if constexpr (W == 1) p[0] = (T)f[0];
-  else vstore16(p, f);
+  if constexpr (W == 1) {
+    p[0] = (T)f[0];
+  } else {
+    constexpr int E = VecTraits<T>::kElems;
+    static_assert(W % E == 0, "W is 1 or whole 16-B vectors");
+#pragma unroll
+    for (int q = 0; q < W / E; ++q) vstore16(p + q * E, f + q * E);
+  }
+}
+
+// W zeros (a fused zero fill)
+template <int W, typename T>
+DEVINL void vzero(T* p) {
+  const float z[W] = {};
+  vstore<W>(p, z);
 }
 
 // Row walker: the block's threads stride a row of C elements, as 16-B vectors
@@ -122,6 +142,26 @@ DEVINL void row_walk(int C, F&& body) {
     for (int c = threadIdx.x; c < C; c += blockDim.x)
       body(c, std::integral_constant<int, 1>{});
   }
+}
+
+// Flat walker of the streaming kernels: the grid strides n elements as
+// vectors of V (thread t of the grid takes vectors t, t + threads, ...), then
+// the n % V tail elements, one per thread. Calls body(element offset,
+// integral_constant<int, W>) with W = V, then W = 1; a thread sees its
+// elements in that order (the chained reductions depend on it). Launched on
+// elementwise_grid blocks; the walker holds no arithmetic. The block size is
+// read with the builtin: blockDim.x inside a device function keeps the
+// non-uniform-block select and costs every kernel a load and ~20 instructions.
+template <int V, typename F>
+DEVINL void flat_walk(long long n, F&& body) {
+  const long long block = __builtin_amdgcn_workgroup_size_x();  // blockDim.x
+  const long long first = blockIdx.x * block + threadIdx.x;
+  const long long step = gridDim.x * block;
+  const long long nvec = n / V;
+  for (long long i = first; i < nvec; i += step)
+    body(i * V, std::integral_constant<int, V>{});
+  for (long long i = nvec * V + first; i < n; i += step)
+    body(i, std::integral_constant<int, 1>{});
 }
 
 // ---- per-sequence lengths (attention) ------------------------------------
@@ -140,6 +180,14 @@ void dispatch2(bool a, bool b, F&& f) {
     if (b) f(A, std::true_type{}); else f(A, std::false_type{});
   };
   if (a) on_a(std::true_type{}); else on_a(std::false_type{});
+}
+
+// Host dispatch over the element type: f(TypeTag<bf16>) or f(TypeTag<float>)
+template <typename T>
+struct TypeTag { using type = T; };
+template <typename F>
+void dispatch_dtype(bool is_bf16, F&& f) {
+  if (is_bf16) f(TypeTag<bf16>{}); else f(TypeTag<float>{});
 }
 
 // ---- reductions ----------------------------------------------------------

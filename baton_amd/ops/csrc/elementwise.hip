@@ -1,52 +1,40 @@
 // Elementwise kernels (gfx950): ReLU, residual add+ReLU, GELU — the glue
-// ops of the model zoo, vectorized to 16 B/lane (G13), grid-stride.
+// ops of the model zoo. A kernel is one body over flat_walk (common.h); the
+// two GELU kernels keep their own loops (note at gelu_fwd_kernel).
 #include "common.h"
 
 template <typename T>
 __global__ void relu_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
                                 long long n) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
-  const long long nvec = n / V;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    typename VT::VecT xv = reinterpret_cast<const typename VT::VecT*>(x)[i];
-    float f[V];
-    VT::to_float(xv, f);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float f[W];
+    vload<W>(x + e, f);
 #pragma unroll
-    for (int k = 0; k < V; ++k) f[k] = fmaxf(f[k], 0.f);
-    typename VT::VecT ov;
-    VT::from_float(f, ov);
-    reinterpret_cast<typename VT::VecT*>(y)[i] = ov;
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x)
-    y[i] = (T)fmaxf((float)x[i], 0.f);
+    for (int k = 0; k < W; ++k) f[k] = fmaxf(f[k], 0.f);
+    vstore<W>(y + e, f);
+  });
 }
 
 // dx = dy * (y > 0)
 template <typename T>
 __global__ void relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y,
                                 T* __restrict__ dx, long long n) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
-  const long long nvec = n / V;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    typename VT::VecT dv = reinterpret_cast<const typename VT::VecT*>(dy)[i];
-    typename VT::VecT yv = reinterpret_cast<const typename VT::VecT*>(y)[i];
-    float df[V], yf[V];
-    VT::to_float(dv, df);
-    VT::to_float(yv, yf);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float df[W], yf[W];
+    if constexpr (W == 1) {
+      // the tail reads dy only where y > 0, as it always has
+      vload<W>(y + e, yf);
+      df[0] = yf[0] > 0.f ? (float)dy[e] : 0.f;
+    } else {
+      vload<W>(dy + e, df);
+      vload<W>(y + e, yf);
 #pragma unroll
-    for (int k = 0; k < V; ++k) df[k] = yf[k] > 0.f ? df[k] : 0.f;
-    typename VT::VecT ov;
-    VT::from_float(df, ov);
-    reinterpret_cast<typename VT::VecT*>(dx)[i] = ov;
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x)
-    dx[i] = (T)((float)y[i] > 0.f ? (float)dy[i] : 0.f);
+      for (int k = 0; k < W; ++k) df[k] = yf[k] > 0.f ? df[k] : 0.f;
+    }
+    vstore<W>(dx + e, df);
+  });
 }
 
 // y = relu(a + b) — the ResNet residual join, fused
@@ -54,25 +42,15 @@ template <typename T>
 __global__ void add_relu_fwd_kernel(const T* __restrict__ a,
                                     const T* __restrict__ b, T* __restrict__ y,
                                     long long n) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
-  const long long nvec = n / V;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    typename VT::VecT av = reinterpret_cast<const typename VT::VecT*>(a)[i];
-    typename VT::VecT bv = reinterpret_cast<const typename VT::VecT*>(b)[i];
-    float af[V], bf[V];
-    VT::to_float(av, af);
-    VT::to_float(bv, bf);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float af[W], bf[W];
+    vload<W>(a + e, af);
+    vload<W>(b + e, bf);
 #pragma unroll
-    for (int k = 0; k < V; ++k) af[k] = fmaxf(af[k] + bf[k], 0.f);
-    typename VT::VecT ov;
-    VT::from_float(af, ov);
-    reinterpret_cast<typename VT::VecT*>(y)[i] = ov;
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x)
-    y[i] = (T)fmaxf((float)a[i] + (float)b[i], 0.f);
+    for (int k = 0; k < W; ++k) af[k] = fmaxf(af[k] + bf[k], 0.f);
+    vstore<W>(y + e, af);
+  });
 }
 
 // z = a + alpha * b — the LoRA combine (base + scaling * delta), fused:
@@ -83,48 +61,29 @@ __global__ void add_scaled_fwd_kernel(const T* __restrict__ a,
                                       const T* __restrict__ b,
                                       T* __restrict__ z, float alpha,
                                       long long n) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
-  const long long nvec = n / V;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    typename VT::VecT av = reinterpret_cast<const typename VT::VecT*>(a)[i];
-    typename VT::VecT bv = reinterpret_cast<const typename VT::VecT*>(b)[i];
-    float af[V], bf[V];
-    VT::to_float(av, af);
-    VT::to_float(bv, bf);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float af[W], bf[W];
+    vload<W>(a + e, af);
+    vload<W>(b + e, bf);
 #pragma unroll
-    for (int k = 0; k < V; ++k) af[k] = fmaf(alpha, bf[k], af[k]);
-    typename VT::VecT ov;
-    VT::from_float(af, ov);
-    reinterpret_cast<typename VT::VecT*>(z)[i] = ov;
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x)
-    z[i] = (T)fmaf(alpha, (float)b[i], (float)a[i]);
+    for (int k = 0; k < W; ++k) af[k] = fmaf(alpha, bf[k], af[k]);
+    vstore<W>(z + e, af);
+  });
 }
 
 // z = alpha * x (the add_scaled backward for the delta operand)
 template <typename T>
 __global__ void scale_fwd_kernel(const T* __restrict__ x, T* __restrict__ z,
                                  float alpha, long long n) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
-  const long long nvec = n / V;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    typename VT::VecT xv = reinterpret_cast<const typename VT::VecT*>(x)[i];
-    float f[V];
-    VT::to_float(xv, f);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float f[W];
+    vload<W>(x + e, f);
 #pragma unroll
-    for (int k = 0; k < V; ++k) f[k] *= alpha;
-    typename VT::VecT ov;
-    VT::from_float(f, ov);
-    reinterpret_cast<typename VT::VecT*>(z)[i] = ov;
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x)
-    z[i] = (T)(alpha * (float)x[i]);
+    for (int k = 0; k < W; ++k) f[k] *= alpha;
+    vstore<W>(z + e, f);
+  });
 }
 
 // tanh-approx GELU (BERT): y = 0.5x(1+tanh(0.79788456(x+0.044715x^3)))
@@ -133,6 +92,8 @@ DEVINL float gelu_of(float v) {
   return 0.5f * v * (1.f + tanhf(inner));
 }
 
+// Hand-written: over flat_walk the compiler packs the arithmetic after tanhf
+// (v_pk_*), another instruction mix and up to 8 more VGPRs (gelu_bwd<bf16>).
 template <typename T>
 __global__ void gelu_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
                                 long long n) {
@@ -158,6 +119,7 @@ DEVINL float gelu_grad(float v) {
   return 0.5f * (1.f + t) + 0.5f * v * (1.f - t * t) * dinner;
 }
 
+// Hand-written, see gelu_fwd_kernel.
 template <typename T>
 __global__ void gelu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                 T* __restrict__ dx, long long n) {
@@ -177,100 +139,75 @@ __global__ void gelu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ 
     dx[i] = (T)((float)dy[i] * gelu_grad((float)x[i]));
 }
 
-#define INST_EW(T)                                                           \
-  template __global__ void relu_fwd_kernel<T>(const T*, T*, long long);      \
-  template __global__ void relu_bwd_kernel<T>(const T*, const T*, T*,        \
-                                              long long);                    \
-  template __global__ void add_relu_fwd_kernel<T>(const T*, const T*, T*,    \
-                                                  long long);                \
-  template __global__ void add_scaled_fwd_kernel<T>(const T*, const T*, T*,  \
-                                                    float, long long);       \
-  template __global__ void scale_fwd_kernel<T>(const T*, T*, float,          \
-                                               long long);                   \
-  template __global__ void gelu_fwd_kernel<T>(const T*, T*, long long);      \
-  template __global__ void gelu_bwd_kernel<T>(const T*, const T*, T*,        \
-                                              long long);
-
-INST_EW(float)
-INST_EW(bf16)
-
 // ---- launchers -------------------------------------------------------------
 #include "launchers.h"
 
 void launch_relu_fwd(bool is_bf16, const void* x, void* y, long long n,
                      hipStream_t s) {
   const int grid = elementwise_grid(n / 8 + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(relu_fwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
-                       (const bf16*)x, (bf16*)y, n);
-  else
-    hipLaunchKernelGGL(relu_fwd_kernel<float>, dim3(grid), dim3(kBlock), 0, s,
-                       (const float*)x, (float*)y, n);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(relu_fwd_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)x, (T*)y, n);
+  });
 }
 
 void launch_relu_bwd(bool is_bf16, const void* dy, const void* y, void* dx,
                      long long n, hipStream_t s) {
   const int grid = elementwise_grid(n / 8 + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(relu_bwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
-                       (const bf16*)dy, (const bf16*)y, (bf16*)dx, n);
-  else
-    hipLaunchKernelGGL(relu_bwd_kernel<float>, dim3(grid), dim3(kBlock), 0, s,
-                       (const float*)dy, (const float*)y, (float*)dx, n);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(relu_bwd_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)dy, (const T*)y, (T*)dx, n);
+  });
 }
 
 void launch_add_relu_fwd(bool is_bf16, const void* a, const void* b, void* y,
                          long long n, hipStream_t s) {
   const int grid = elementwise_grid(n / 8 + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(add_relu_fwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0,
-                       s, (const bf16*)a, (const bf16*)b, (bf16*)y, n);
-  else
-    hipLaunchKernelGGL(add_relu_fwd_kernel<float>, dim3(grid), dim3(kBlock), 0,
-                       s, (const float*)a, (const float*)b, (float*)y, n);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(add_relu_fwd_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)a, (const T*)b, (T*)y, n);
+  });
 }
 
 void launch_add_scaled_fwd(bool is_bf16, const void* a, const void* b, void* z,
                            float alpha, long long n, hipStream_t s) {
   const int grid = elementwise_grid(n / 8 + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(add_scaled_fwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0,
-                       s, (const bf16*)a, (const bf16*)b, (bf16*)z, alpha, n);
-  else
-    hipLaunchKernelGGL(add_scaled_fwd_kernel<float>, dim3(grid), dim3(kBlock),
-                       0, s, (const float*)a, (const float*)b, (float*)z, alpha,
-                       n);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(add_scaled_fwd_kernel<T>, dim3(grid), dim3(kBlock), 0,
+                       s, (const T*)a, (const T*)b, (T*)z, alpha, n);
+  });
 }
 
 void launch_scale_fwd(bool is_bf16, const void* x, void* z, float alpha,
                       long long n, hipStream_t s) {
   const int grid = elementwise_grid(n / 8 + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(scale_fwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
-                       (const bf16*)x, (bf16*)z, alpha, n);
-  else
-    hipLaunchKernelGGL(scale_fwd_kernel<float>, dim3(grid), dim3(kBlock), 0, s,
-                       (const float*)x, (float*)z, alpha, n);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(scale_fwd_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)x, (T*)z, alpha, n);
+  });
 }
 
 void launch_gelu_fwd(bool is_bf16, const void* x, void* y, long long n,
                      hipStream_t s) {
   const int grid = elementwise_grid(n / 4 + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(gelu_fwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
-                       (const bf16*)x, (bf16*)y, n);
-  else
-    hipLaunchKernelGGL(gelu_fwd_kernel<float>, dim3(grid), dim3(kBlock), 0, s,
-                       (const float*)x, (float*)y, n);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(gelu_fwd_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)x, (T*)y, n);
+  });
 }
 
 void launch_gelu_bwd(bool is_bf16, const void* dy, const void* x, void* dx,
                      long long n, hipStream_t s) {
   const int grid = elementwise_grid(n / 4 + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(gelu_bwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
-                       (const bf16*)dy, (const bf16*)x, (bf16*)dx, n);
-  else
-    hipLaunchKernelGGL(gelu_bwd_kernel<float>, dim3(grid), dim3(kBlock), 0, s,
-                       (const float*)dy, (const float*)x, (float*)dx, n);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(gelu_bwd_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)dy, (const T*)x, (T*)dx, n);
+  });
 }

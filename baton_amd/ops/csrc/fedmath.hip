@@ -4,7 +4,7 @@
 // theta-traffic pattern: each GPU-client writes (n_i/N) * theta_i into the
 // fp32 reduce buffer (scale_cast), RCCL reduces to root, root broadcasts,
 // every client installs the result back into its (possibly bf16) params
-// (cast_copy). All streaming ops: 16 B/lane, grid-stride.
+// (cast_copy). All streaming ops, each one body over flat_walk (common.h).
 #include "common.h"
 
 // dst(f32) = alpha * src(T)
@@ -12,25 +12,14 @@ template <typename T>
 __global__ void scale_cast_kernel(float* __restrict__ dst,
                                   const T* __restrict__ src, long long n,
                                   float alpha) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
-  const long long nvec = n / V;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    typename VT::VecT sv = reinterpret_cast<const typename VT::VecT*>(src)[i];
-    float f[V];
-    VT::to_float(sv, f);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float f[W];
+    vload<W>(src + e, f);
 #pragma unroll
-    for (int q = 0; q < V / 4; ++q) {
-      f32x4 o;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = alpha * f[q * 4 + k];
-      reinterpret_cast<f32x4*>(dst)[i * (V / 4) + q] = o;
-    }
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x)
-    dst[i] = alpha * (float)src[i];
+    for (int k = 0; k < W; ++k) f[k] = alpha * f[k];
+    vstore<W>(dst + e, f);
+  });
 }
 
 // f32 -> 16-B vector for cast_copy's body. bf16 rounds to nearest even as
@@ -52,54 +41,39 @@ DEVINL void cast_from_float(const float* in, s16x8& v) {
   }
 }
 
-// dst(T) = src(f32)
+// dst(T) = src(f32): cast_from_float in the body, the (T) conversion in the
+// tail
 template <typename T>
 __global__ void cast_copy_kernel(T* __restrict__ dst,
                                  const float* __restrict__ src, long long n) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
-  const long long nvec = n / V;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    float f[V];
-#pragma unroll
-    for (int q = 0; q < V / 4; ++q) {
-      f32x4 s = reinterpret_cast<const f32x4*>(src)[i * (V / 4) + q];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) f[q * 4 + k] = s[k];
+  using VecT = typename VecTraits<T>::VecT;
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float f[W];
+    vload<W>(src + e, f);
+    if constexpr (W == 1) {
+      vstore<1>(dst + e, f);
+    } else {
+      VecT o;
+      cast_from_float(f, o);
+      *reinterpret_cast<VecT*>(dst + e) = o;
     }
-    typename VT::VecT o;
-    cast_from_float(f, o);
-    reinterpret_cast<typename VT::VecT*>(dst)[i] = o;
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x)
-    dst[i] = (T)src[i];
+  });
 }
 
 // y = a*x + b*y (fp32) — the generalized aggregation update
 __global__ void axpby_kernel(float* __restrict__ y, const float* __restrict__ x,
                              long long n, float a, float b) {
-  const long long nvec = n / 4;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
-    f32x4 yv = reinterpret_cast<const f32x4*>(y)[i];
+  flat_walk<4>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float xf[W], yf[W];
+    vload<W>(x + e, xf);
+    vload<W>(y + e, yf);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) yv[k] = fmaf(a, xv[k], b * yv[k]);
-    reinterpret_cast<f32x4*>(y)[i] = yv;
-  }
-  for (long long i = nvec * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x)
-    y[i] = fmaf(a, x[i], b * y[i]);
+    for (int k = 0; k < W; ++k) yf[k] = fmaf(a, xf[k], b * yf[k]);
+    vstore<W>(y + e, yf);
+  });
 }
-
-template __global__ void scale_cast_kernel<float>(float*, const float*,
-                                                  long long, float);
-template __global__ void scale_cast_kernel<bf16>(float*, const bf16*, long long,
-                                                 float);
-template __global__ void cast_copy_kernel<float>(float*, const float*, long long);
-template __global__ void cast_copy_kernel<bf16>(bf16*, const float*, long long);
 
 // ---- launchers -------------------------------------------------------------
 #include "launchers.h"
@@ -107,23 +81,21 @@ template __global__ void cast_copy_kernel<bf16>(bf16*, const float*, long long);
 void launch_scale_cast(bool src_bf16, float* dst, const void* src, long long n,
                        float alpha, hipStream_t s) {
   const int grid = elementwise_grid(n / 8 + 1);
-  if (src_bf16)
-    hipLaunchKernelGGL(scale_cast_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
-                       dst, (const bf16*)src, n, alpha);
-  else
-    hipLaunchKernelGGL(scale_cast_kernel<float>, dim3(grid), dim3(kBlock), 0, s,
-                       dst, (const float*)src, n, alpha);
+  dispatch_dtype(src_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(scale_cast_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       dst, (const T*)src, n, alpha);
+  });
 }
 
 void launch_cast_copy(bool dst_bf16, void* dst, const float* src, long long n,
                       hipStream_t s) {
   const int grid = elementwise_grid(n / 8 + 1);
-  if (dst_bf16)
-    hipLaunchKernelGGL(cast_copy_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
-                       (bf16*)dst, src, n);
-  else
-    hipLaunchKernelGGL(cast_copy_kernel<float>, dim3(grid), dim3(kBlock), 0, s,
-                       (float*)dst, src, n);
+  dispatch_dtype(dst_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(cast_copy_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (T*)dst, src, n);
+  });
 }
 
 void launch_axpby(float* y, const float* x, long long n, float a, float b,

@@ -7,9 +7,10 @@
 // alpha * coef * d into the fp32 reduce buffer (delta_scale_cast_kernel); a
 // client whose norm is not finite sends +0.0 and weight 0. The root turns the
 // reduced weight W into round_state (fedopt_finalize_kernel) and applies
-// Delta = D / W to x, m and v (server_step_kernel). All state is fp32, all
-// kernels use the optim.hip geometry (optim_grid blocks of 256 threads, 16 B
-// per lane, scalar tail, grid-stride), and nothing is read back by the host.
+// Delta = D / W to x, m and v (server_step_kernel). All state is fp32, the
+// kernels run flat_walk's geometry (common.h) on optim_grid blocks, the client
+// side as bodies over it and the server step by hand (note at
+// dp_noise_kernel), and nothing is read back by the host.
 //
 // DP-FedAvg (server_step_kernel<MODE, true>, dp_noise_kernel): Delta =
 // fl(D + xi) with xi = fl(sigma * zeta) and zeta the Philox4x32-10 unit normal
@@ -25,43 +26,32 @@
 // ---- client side -----------------------------------------------------------
 
 // grad_sumsq_kernel on float(theta) - x: every thread chains fma(d, d, acc)
-// over the vectors of its grid stride in order, then at most one tail
-// element; one partial per block at partials[blockIdx.x], no atomics.
+// over its elements in flat_walk's order; one partial per block at
+// partials[blockIdx.x], no atomics.
 template <typename T>
 __global__ void delta_sumsq_kernel(const T* __restrict__ theta,
                                    const float* __restrict__ x, long long n,
                                    float* __restrict__ partials) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
   __shared__ float scratch[kBlock / kWave];
-  const long long nvec = n / V;
   float acc = 0.f;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    float tf[V];
-    VT::to_float(reinterpret_cast<const typename VT::VecT*>(theta)[i], tf);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float tf[W], xf[W];
+    vload<W>(theta + e, tf);
+    vload<W>(x + e, xf);
 #pragma unroll
-    for (int q = 0; q < V / 4; ++q) {
-      const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i * (V / 4) + q];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float d = tf[q * 4 + k] - xv[k];
-        acc = fmaf(d, d, acc);
-      }
+    for (int k = 0; k < W; ++k) {
+      const float d = tf[k] - xf[k];
+      acc = fmaf(d, d, acc);
     }
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float d = (float)theta[i] - x[i];
-    acc = fmaf(d, d, acc);
-  }
+  });
   const float total = block_reduce_sum(acc, scratch);
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
 // dst = (alpha * coef) * (float(theta) - x), clip_state as clip_finalize
 // wrote it. A non-finite client ([2] == 0) stores +0.0 and never reads theta:
-// a uniform branch in front of the loop, so 0 * inf is never formed. w_out
+// a uniform branch in front of the walk, so 0 * inf is never formed. w_out
 // (may be null) receives the weight this client contributes to W.
 template <typename T>
 __global__ void delta_scale_cast_kernel(float* __restrict__ dst,
@@ -70,42 +60,26 @@ __global__ void delta_scale_cast_kernel(float* __restrict__ dst,
                                         long long n, float alpha,
                                         const float* __restrict__ clip_state,
                                         float* __restrict__ w_out) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
-  const long long nvec = n / V;
+  constexpr int V = VecTraits<T>::kElems;
   const bool finite = clip_state[2] != 0.f;
   if (w_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
     w_out[0] = finite ? alpha : 0.f;
   if (!finite) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-         i < nvec; i += (long long)gridDim.x * blockDim.x) {
-#pragma unroll
-      for (int q = 0; q < V / 4; ++q)
-        reinterpret_cast<f32x4*>(dst)[i * (V / 4) + q] = f32x4{};
-    }
-    for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x +
-                       threadIdx.x;
-         i < n; i += (long long)gridDim.x * blockDim.x)
-      dst[i] = 0.f;
+    flat_walk<V>(n, [&](long long e, auto w) {
+      vzero<decltype(w)::value>(dst + e);
+    });
     return;
   }
   const float s = alpha * clip_state[1];
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    float tf[V];
-    VT::to_float(reinterpret_cast<const typename VT::VecT*>(theta)[i], tf);
+  flat_walk<V>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float tf[W], xf[W];
+    vload<W>(theta + e, tf);
+    vload<W>(x + e, xf);
 #pragma unroll
-    for (int q = 0; q < V / 4; ++q) {
-      const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i * (V / 4) + q];
-      f32x4 o;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = s * (tf[q * 4 + k] - xv[k]);
-      reinterpret_cast<f32x4*>(dst)[i * (V / 4) + q] = o;
-    }
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x)
-    dst[i] = s * ((float)theta[i] - x[i]);
+    for (int k = 0; k < W; ++k) tf[k] = s * (tf[k] - xf[k]);
+    vstore<W>(dst + e, tf);
+  });
 }
 
 // ---- server side -----------------------------------------------------------
@@ -187,6 +161,9 @@ DEVINL void unit_normals4(const DpNoise& nz, long long j, float (&z)[4]) {
 
 // xi = fl(sigma * zeta) alone, on server_step_kernel's index walk: one Philox
 // call per f32x4, the tail from block (elem_offset + n) >> 2.
+// This kernel and server_step_kernel keep their own loops: here the tail's
+// block is loop-invariant and its Philox call leaves the loop; over flat_walk
+// it is recomputed per element (dp_noise 36 -> 52 VGPRs, twice the sqrt / log).
 __global__ void dp_noise_kernel(float* __restrict__ out, long long n,
                                 DpNoise nz) {
   const long long nvec = n / 4;
@@ -306,12 +283,11 @@ __global__ void server_step_kernel(const float* __restrict__ D,
 int launch_delta_sumsq(bool is_bf16, const void* theta, const float* x,
                        long long n, float* partials, hipStream_t s) {
   const int grid = optim_grid(n);
-  if (is_bf16)
-    hipLaunchKernelGGL(delta_sumsq_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
-                       (const bf16*)theta, x, n, partials);
-  else
-    hipLaunchKernelGGL(delta_sumsq_kernel<float>, dim3(grid), dim3(kBlock), 0,
-                       s, (const float*)theta, x, n, partials);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(delta_sumsq_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)theta, x, n, partials);
+  });
   return grid;
 }
 
@@ -320,14 +296,11 @@ void launch_delta_scale_cast(bool is_bf16, float* dst, const void* theta,
                              const float* clip_state, float* w_out,
                              hipStream_t s) {
   const int grid = optim_grid(n);
-  if (is_bf16)
-    hipLaunchKernelGGL(delta_scale_cast_kernel<bf16>, dim3(grid), dim3(kBlock),
-                       0, s, dst, (const bf16*)theta, x, n, alpha, clip_state,
-                       w_out);
-  else
-    hipLaunchKernelGGL(delta_scale_cast_kernel<float>, dim3(grid), dim3(kBlock),
-                       0, s, dst, (const float*)theta, x, n, alpha, clip_state,
-                       w_out);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(delta_scale_cast_kernel<T>, dim3(grid), dim3(kBlock), 0,
+                       s, dst, (const T*)theta, x, n, alpha, clip_state, w_out);
+  });
 }
 
 void launch_fedopt_finalize(const float* w_sum, float* round_state,
@@ -336,22 +309,27 @@ void launch_fedopt_finalize(const float* w_sum, float* round_state,
                      round_state);
 }
 
+// Host dispatch over the server optimizer: f(integral_constant<int, MODE>)
+template <typename F>
+static void dispatch_server_mode(int mode, F&& f) {
+  switch (mode) {
+    case kServerMean: f(std::integral_constant<int, kServerMean>{}); break;
+    case kServerAvgM: f(std::integral_constant<int, kServerAvgM>{}); break;
+    case kServerAdagrad: f(std::integral_constant<int, kServerAdagrad>{}); break;
+    case kServerAdam: f(std::integral_constant<int, kServerAdam>{}); break;
+    default: f(std::integral_constant<int, kServerYogi>{}); break;
+  }
+}
+
 void launch_server_step(int mode, const float* D, float* x, float* m, float* v,
                         long long n, float lr, float b1, float b2, float tau,
                         const float* round_state, hipStream_t s) {
   const int grid = optim_grid(n);
-#define BATON_SERVER_STEP(MODE)                                                \
-  hipLaunchKernelGGL((server_step_kernel<MODE, false>), dim3(grid),           \
-                     dim3(kBlock), 0, s, D, x, m, v, n, lr, b1, b2, tau,      \
-                     round_state)
-  switch (mode) {
-    case kServerMean: BATON_SERVER_STEP(kServerMean); break;
-    case kServerAvgM: BATON_SERVER_STEP(kServerAvgM); break;
-    case kServerAdagrad: BATON_SERVER_STEP(kServerAdagrad); break;
-    case kServerAdam: BATON_SERVER_STEP(kServerAdam); break;
-    default: BATON_SERVER_STEP(kServerYogi); break;
-  }
-#undef BATON_SERVER_STEP
+  dispatch_server_mode(mode, [&](auto md) {
+    hipLaunchKernelGGL((server_step_kernel<decltype(md)::value, false>),
+                       dim3(grid), dim3(kBlock), 0, s, D, x, m, v, n, lr, b1,
+                       b2, tau, round_state);
+  });
 }
 
 static DpNoise dp_noise_args(unsigned long long seed, unsigned round,
@@ -369,18 +347,11 @@ void launch_server_step_noise(int mode, const float* D, float* x, float* m,
                               float sigma, hipStream_t s) {
   const int grid = optim_grid(n);
   const DpNoise nz = dp_noise_args(seed, round, stream, elem_offset, sigma);
-#define BATON_SERVER_STEP(MODE)                                                \
-  hipLaunchKernelGGL((server_step_kernel<MODE, true, DpNoise>), dim3(grid),   \
-                     dim3(kBlock), 0, s, D, x, m, v, n, lr, b1, b2, tau,      \
-                     round_state, nz)
-  switch (mode) {
-    case kServerMean: BATON_SERVER_STEP(kServerMean); break;
-    case kServerAvgM: BATON_SERVER_STEP(kServerAvgM); break;
-    case kServerAdagrad: BATON_SERVER_STEP(kServerAdagrad); break;
-    case kServerAdam: BATON_SERVER_STEP(kServerAdam); break;
-    default: BATON_SERVER_STEP(kServerYogi); break;
-  }
-#undef BATON_SERVER_STEP
+  dispatch_server_mode(mode, [&](auto md) {
+    hipLaunchKernelGGL((server_step_kernel<decltype(md)::value, true, DpNoise>),
+                       dim3(grid), dim3(kBlock), 0, s, D, x, m, v, n, lr, b1,
+                       b2, tau, round_state, nz);
+  });
 }
 
 void launch_dp_noise(float* out, long long n, unsigned long long seed,

@@ -122,6 +122,8 @@ DEVINL float kept_sum(float (&v)[K], int k, int b) {
 // (a multiple of 4, base 16-byte aligned). round_state[2] == 0 is a uniform
 // early exit: a skipped round writes nothing. Every row is loaded, then a dead
 // row's values are replaced by +inf with a select: no branch around a load.
+// Hand-written loops (flat_walk's geometry): over the walker K = 13 takes 26
+// more VGPRs and K >= 15 spills SGPRs.
 template <int K>
 __global__ void robust_select_kernel(float* __restrict__ D,
                                      const float* __restrict__ U,

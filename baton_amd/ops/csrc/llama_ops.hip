@@ -2,9 +2,10 @@
 // LayerNorm's kernels in norm.hip.)
 //
 // BASELINE.json config 4 (Llama-3-8B LoRA federated fine-tune). Both are
-// memory-bound streaming ops: vectorized loads where layout permits, fp32
-// math, grid-stride. RoPE uses host-precomputed cos/sin tables (guide
-// Appendix B: on-device trig turns a memory-bound op VALU-bound).
+// memory-bound streaming ops in fp32 math: SwiGLU is two bodies over flat_walk
+// (common.h), RoPE a grid-stride loop over pairs. RoPE uses host-precomputed
+// cos/sin tables (guide Appendix B: on-device trig turns a memory-bound op
+// VALU-bound).
 #include "common.h"
 
 // ---- RoPE (neox half-rotation) ---------------------------------------------
@@ -49,26 +50,18 @@ template <typename T>
 __global__ void silu_mul_fwd_kernel(const T* __restrict__ a,
                                     const T* __restrict__ b, T* __restrict__ y,
                                     long long n) {
-  constexpr int V = VecTraits<T>::kElems;
-  const long long nvec = n / V;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    float fa[V], fb[V];
-    vload16(a + i * V, fa);
-    vload16(b + i * V, fb);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float fa[W], fb[W];
+    vload<W>(a + e, fa);
+    vload<W>(b + e, fb);
 #pragma unroll
-    for (int q = 0; q < V; ++q) {
+    for (int q = 0; q < W; ++q) {
       float sig = 1.f / (1.f + __expf(-fa[q]));
       fa[q] = fa[q] * sig * fb[q];
     }
-    vstore16(y + i * V, fa);
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x) {
-    float av = (float)a[i];
-    float sig = 1.f / (1.f + __expf(-av));
-    y[i] = (T)(av * sig * (float)b[i]);
-  }
+    vstore<W>(y + e, fa);
+  });
 }
 
 template <typename T>
@@ -76,35 +69,23 @@ __global__ void silu_mul_bwd_kernel(const T* __restrict__ dy,
                                     const T* __restrict__ a,
                                     const T* __restrict__ b, T* __restrict__ da,
                                     T* __restrict__ db, long long n) {
-  constexpr int V = VecTraits<T>::kElems;
-  const long long nvec = n / V;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    float fa[V], fb[V], fd[V], fda[V], fdb[V];
-    vload16(a + i * V, fa);
-    vload16(b + i * V, fb);
-    vload16(dy + i * V, fd);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float fa[W], fb[W], fd[W], fda[W], fdb[W];
+    vload<W>(a + e, fa);
+    vload<W>(b + e, fb);
+    vload<W>(dy + e, fd);
 #pragma unroll
-    for (int q = 0; q < V; ++q) {
+    for (int q = 0; q < W; ++q) {
       float sig = 1.f / (1.f + __expf(-fa[q]));
       float silu = fa[q] * sig;
       float dsilu = sig * fmaf(fa[q], 1.f - sig, 1.f);
       fda[q] = fd[q] * fb[q] * dsilu;
       fdb[q] = fd[q] * silu;
     }
-    vstore16(da + i * V, fda);
-    vstore16(db + i * V, fdb);
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x) {
-    float av = (float)a[i];
-    float dyv = (float)dy[i];
-    float sig = 1.f / (1.f + __expf(-av));
-    float silu = av * sig;
-    float dsilu = sig * fmaf(av, 1.f - sig, 1.f);
-    da[i] = (T)(dyv * (float)b[i] * dsilu);
-    db[i] = (T)(dyv * silu);
-  }
+    vstore<W>(da + e, fda);
+    vstore<W>(db + e, fdb);
+  });
 }
 
 #define INST_LLAMA(T)                                                          \
@@ -113,11 +94,7 @@ __global__ void silu_mul_bwd_kernel(const T* __restrict__ dy,
                                                  int, int);                    \
   template __global__ void rope_kernel<T, true>(const T*, T*, const float*,    \
                                                 const float*, long long, int,  \
-                                                int, int);                     \
-  template __global__ void silu_mul_fwd_kernel<T>(const T*, const T*, T*,      \
-                                                  long long);                  \
-  template __global__ void silu_mul_bwd_kernel<T>(const T*, const T*,          \
-                                                  const T*, T*, T*, long long);
+                                                int, int);
 
 INST_LLAMA(float)
 INST_LLAMA(bf16)
@@ -140,24 +117,21 @@ void launch_rope(bool is_bf16, bool inverse, const void* x, void* y,
 void launch_silu_mul_fwd(bool is_bf16, const void* a, const void* b, void* y,
                          long long n, hipStream_t s) {
   const int grid = elementwise_grid(n / 4 + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(silu_mul_fwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0,
-                       s, (const bf16*)a, (const bf16*)b, (bf16*)y, n);
-  else
-    hipLaunchKernelGGL(silu_mul_fwd_kernel<float>, dim3(grid), dim3(kBlock), 0,
-                       s, (const float*)a, (const float*)b, (float*)y, n);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(silu_mul_fwd_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)a, (const T*)b, (T*)y, n);
+  });
 }
 
 void launch_silu_mul_bwd(bool is_bf16, const void* dy, const void* a,
                          const void* b, void* da, void* db, long long n,
                          hipStream_t s) {
   const int grid = elementwise_grid(n / 4 + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(silu_mul_bwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0,
-                       s, (const bf16*)dy, (const bf16*)a, (const bf16*)b,
-                       (bf16*)da, (bf16*)db, n);
-  else
-    hipLaunchKernelGGL(silu_mul_bwd_kernel<float>, dim3(grid), dim3(kBlock), 0,
-                       s, (const float*)dy, (const float*)a, (const float*)b,
-                       (float*)da, (float*)db, n);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(silu_mul_bwd_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)dy, (const T*)a, (const T*)b, (T*)da, (T*)db,
+                       n);
+  });
 }

@@ -1,41 +1,31 @@
 // Loss kernels (gfx950): MSE and cross-entropy, forward + backward.
 //
-// The reference uses nn.MSELoss on CPU (/root/reference/demo.py:32,44);
-// classifier configs (ResNet/BERT) need CE. Both are fused single-pass
-// kernels: MSE is a grid-stride reduce; CE is one block per row with an
-// online log-sum-exp (no materialized softmax in the forward).
+// Both are fused single-pass kernels: MSE is a reduce over flat_walk
+// (common.h); CE (the classifier configs, ResNet/BERT) is one block per row
+// with an online log-sum-exp (no materialized softmax in the forward).
 #include "common.h"
 
 // ---- MSE ------------------------------------------------------------------
 
 // partial = sum((x-y)^2); out[0] += partial (atomic). Caller zeroes out and
-// divides by n (mean) on device via the tiny finalize kernel below.
+// divides by n (mean) on device via the tiny finalize kernel below. A thread
+// chains its fmas in flat_walk's order.
 template <typename T>
 __global__ void mse_fwd_kernel(const T* __restrict__ x, const T* __restrict__ y,
                                float* __restrict__ out, long long n) {
   __shared__ float scratch[kBlock / kWave];
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
-  const long long nvec = n / V;
   float acc = 0.f;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    typename VT::VecT xv = reinterpret_cast<const typename VT::VecT*>(x)[i];
-    typename VT::VecT yv = reinterpret_cast<const typename VT::VecT*>(y)[i];
-    float xf[V], yf[V];
-    VT::to_float(xv, xf);
-    VT::to_float(yv, yf);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float xf[W], yf[W];
+    vload<W>(x + e, xf);
+    vload<W>(y + e, yf);
 #pragma unroll
-    for (int k = 0; k < V; ++k) {
+    for (int k = 0; k < W; ++k) {
       float d = xf[k] - yf[k];
       acc = fmaf(d, d, acc);
     }
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x) {
-    float d = (float)x[i] - (float)y[i];
-    acc = fmaf(d, d, acc);
-  }
+  });
   float total = block_reduce_sum(acc, scratch);
   if (threadIdx.x == 0) atomicAdd(out, total);
 }
@@ -49,26 +39,16 @@ template <typename T>
 __global__ void mse_bwd_kernel(const T* __restrict__ x, const T* __restrict__ y,
                                const float* __restrict__ dout,
                                T* __restrict__ dx, long long n) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
   const float c = 2.f * dout[0] / (float)n;
-  const long long nvec = n / V;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    typename VT::VecT xv = reinterpret_cast<const typename VT::VecT*>(x)[i];
-    typename VT::VecT yv = reinterpret_cast<const typename VT::VecT*>(y)[i];
-    float xf[V], yf[V];
-    VT::to_float(xv, xf);
-    VT::to_float(yv, yf);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float xf[W], yf[W];
+    vload<W>(x + e, xf);
+    vload<W>(y + e, yf);
 #pragma unroll
-    for (int k = 0; k < V; ++k) xf[k] = c * (xf[k] - yf[k]);
-    typename VT::VecT ov;
-    VT::from_float(xf, ov);
-    reinterpret_cast<typename VT::VecT*>(dx)[i] = ov;
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x)
-    dx[i] = (T)(c * ((float)x[i] - (float)y[i]));
+    for (int k = 0; k < W; ++k) xf[k] = c * (xf[k] - yf[k]);
+    vstore<W>(dx + e, xf);
+  });
 }
 
 // ---- Cross-entropy ---------------------------------------------------------
@@ -192,14 +172,6 @@ __global__ void ce_bwd_kernel(const T* __restrict__ logits,
   }
 }
 
-template __global__ void mse_fwd_kernel<float>(const float*, const float*,
-                                               float*, long long);
-template __global__ void mse_fwd_kernel<bf16>(const bf16*, const bf16*, float*,
-                                              long long);
-template __global__ void mse_bwd_kernel<float>(const float*, const float*,
-                                               const float*, float*, long long);
-template __global__ void mse_bwd_kernel<bf16>(const bf16*, const bf16*,
-                                              const float*, bf16*, long long);
 #define CE_INSTANTIATE(T)                                                      \
   template __global__ void ce_fwd_kernel<T, false>(                            \
       const T*, const long long*, float*, float*, int, int);                   \
@@ -220,12 +192,11 @@ CE_INSTANTIATE(bf16)
 void launch_mse_fwd(bool is_bf16, const void* x, const void* y, float* out,
                     long long n, hipStream_t s) {
   const int grid = elementwise_grid(n / 8 + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(mse_fwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
-                       (const bf16*)x, (const bf16*)y, out, n);
-  else
-    hipLaunchKernelGGL(mse_fwd_kernel<float>, dim3(grid), dim3(kBlock), 0, s,
-                       (const float*)x, (const float*)y, out, n);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(mse_fwd_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)x, (const T*)y, out, n);
+  });
 }
 
 void launch_scale_scalar(float* out, float scale, hipStream_t s) {
@@ -235,12 +206,11 @@ void launch_scale_scalar(float* out, float scale, hipStream_t s) {
 void launch_mse_bwd(bool is_bf16, const void* x, const void* y,
                     const float* dout, void* dx, long long n, hipStream_t s) {
   const int grid = elementwise_grid(n / 8 + 1);
-  if (is_bf16)
-    hipLaunchKernelGGL(mse_bwd_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
-                       (const bf16*)x, (const bf16*)y, dout, (bf16*)dx, n);
-  else
-    hipLaunchKernelGGL(mse_bwd_kernel<float>, dim3(grid), dim3(kBlock), 0, s,
-                       (const float*)x, (const float*)y, dout, (float*)dx, n);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(mse_bwd_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)x, (const T*)y, dout, (T*)dx, n);
+  });
 }
 
 void launch_ce_fwd(bool is_bf16, const void* logits, const long long* target,

@@ -575,10 +575,7 @@ __global__ void bn_bwd_dx_kernel(const T* __restrict__ x,
 
 // dtype x mode dispatch: calls f(TypeTag<T>, integral_constant<int, mode>)
 // for T = bf16 / float and mode in [0, N), so each launcher names its kernel
-// once and only the listed modes are instantiated.
-template <typename T>
-struct TypeTag { using type = T; };
-
+// once and only the listed modes are instantiated (TypeTag: common.h).
 template <typename T, int N, typename F>
 static void dispatch_mode(int mode, F&& f) {
   if constexpr (N > 0) {

@@ -1,10 +1,10 @@
 // Fused optimizer kernels (gfx950).
 //
-// The reference steps torch.optim.SGD per batch on CPU
-// (/root/reference/demo.py:34,47). Here the whole step is one
-// HBM-rate streaming kernel over a flat buffer (runtime/arena.py):
-// p/g in fp32 or bf16, momentum/Adam moments always fp32.
-// 16 B/lane vectorized (G13), grid-stride, no host sync.
+// The whole step is one HBM-rate streaming kernel over a flat buffer
+// (runtime/arena.py): p/g in fp32 or bf16, momentum/Adam moments always fp32.
+// grad_sumsq and the zero fill are bodies over flat_walk (common.h) on
+// optim_grid blocks; the two step kernels walk the same way by hand (note at
+// sgd_kernel). No host sync.
 #include "common.h"
 
 // Clipping, the non-finite skip and decoupled decay. The EXT instantiations
@@ -40,18 +40,14 @@ DEVINL float ext_grad(float g, float& p, float coef, bool decoupled,
 // A skipped step's only work: the fused zero_grad.
 template <typename T>
 DEVINL void zero_grads(T* __restrict__ g, long long n) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
-  const long long nvec = n / V;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x)
-    reinterpret_cast<typename VT::VecT*>(g)[i] = typename VT::VecT{};
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x)
-    g[i] = (T)0.f;
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    vzero<decltype(w)::value>(g + e);
+  });
 }
 
-// tail == true: scalar path for the last (n % kElems) elements.
+// sgd_kernel and adam_kernel keep their own loops: over flat_walk sgd's tail
+// no longer shares its update of p between the momentum branches (one fma
+// more), and adam<float, EXT> takes 5 more VGPRs with another packed-math mix.
 // zero_after: write zeros back to g after consuming it — fuses the next
 // iteration's zero_grad fill into this pass (one launch fewer per step).
 template <typename T, bool EXT, typename... Ext>
@@ -222,31 +218,22 @@ __global__ void adam_kernel(T* __restrict__ p, T* __restrict__ g,
 }
 
 // ---- global gradient norm ---------------------------------------------------
-// Stage 1: every thread chains fma(x, x, acc) over its elements in fp32 (the
-// vectors of its grid stride in order, then at most one tail element), the
-// block reduces (6 shuffle levels, then the 4 wave sums in order) and stores
-// ONE partial at partials[offset + blockIdx.x]. No atomics: the norm has the
-// same bits in every run.
+// Stage 1: every thread chains fma(x, x, acc) over its elements in fp32, in
+// flat_walk's order, the block reduces (6 shuffle levels, then the 4 wave sums
+// in order) and stores ONE partial at partials[blockIdx.x]. No atomics: the
+// norm has the same bits in every run.
 template <typename T>
 __global__ void grad_sumsq_kernel(const T* __restrict__ g, long long n,
                                   float* __restrict__ partials) {
-  using VT = VecTraits<T>;
-  constexpr int V = VT::kElems;
   __shared__ float scratch[kBlock / kWave];
-  const long long nvec = n / V;
   float acc = 0.f;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-       i += (long long)gridDim.x * blockDim.x) {
-    float gf[V];
-    VT::to_float(reinterpret_cast<const typename VT::VecT*>(g)[i], gf);
+  flat_walk<VecTraits<T>::kElems>(n, [&](long long e, auto w) {
+    constexpr int W = decltype(w)::value;
+    float gf[W];
+    vload<W>(g + e, gf);
 #pragma unroll
-    for (int k = 0; k < V; ++k) acc = fmaf(gf[k], gf[k], acc);
-  }
-  for (long long i = nvec * V + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float x = (float)g[i];
-    acc = fmaf(x, x, acc);
-  }
+    for (int k = 0; k < W; ++k) acc = fmaf(gf[k], gf[k], acc);
+  });
   const float total = block_reduce_sum(acc, scratch);
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
@@ -290,14 +277,11 @@ void launch_sgd(bool is_bf16, void* p, void* g, float* m, long long n,
                 float lr, float momentum, float wd, int zero_after,
                 hipStream_t s) {
   const int grid = optim_grid(n);
-  if (is_bf16)
-    hipLaunchKernelGGL((sgd_kernel<bf16, false>), dim3(grid), dim3(kBlock), 0,
-                       s, (bf16*)p, (bf16*)g, m, n, lr, momentum, wd,
-                       zero_after);
-  else
-    hipLaunchKernelGGL((sgd_kernel<float, false>), dim3(grid), dim3(kBlock), 0,
-                       s, (float*)p, (float*)g, m, n, lr, momentum, wd,
-                       zero_after);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((sgd_kernel<T, false>), dim3(grid), dim3(kBlock), 0, s,
+                       (T*)p, (T*)g, m, n, lr, momentum, wd, zero_after);
+  });
 }
 
 void launch_adam(bool is_bf16, void* p, void* g, float* m, float* v,
@@ -305,14 +289,12 @@ void launch_adam(bool is_bf16, void* p, void* g, float* m, float* v,
                  float inv_bc1, float inv_sqrt_bc2, int zero_after,
                  hipStream_t s) {
   const int grid = optim_grid(n);
-  if (is_bf16)
-    hipLaunchKernelGGL((adam_kernel<bf16, false>), dim3(grid), dim3(kBlock), 0,
-                       s, (bf16*)p, (bf16*)g, m, v, n, lr, b1, b2, eps, wd,
-                       inv_bc1, inv_sqrt_bc2, zero_after);
-  else
-    hipLaunchKernelGGL((adam_kernel<float, false>), dim3(grid), dim3(kBlock), 0,
-                       s, (float*)p, (float*)g, m, v, n, lr, b1, b2, eps, wd,
-                       inv_bc1, inv_sqrt_bc2, zero_after);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((adam_kernel<T, false>), dim3(grid), dim3(kBlock), 0, s,
+                       (T*)p, (T*)g, m, v, n, lr, b1, b2, eps, wd, inv_bc1,
+                       inv_sqrt_bc2, zero_after);
+  });
 }
 
 void launch_sgd_ext(bool is_bf16, void* p, void* g, float* m, long long n,
@@ -320,14 +302,12 @@ void launch_sgd_ext(bool is_bf16, void* p, void* g, float* m, long long n,
                     const float* clip_state, int decoupled, hipStream_t s) {
   const int grid = optim_grid(n);
   const OptExt e{clip_state, decoupled};
-  if (is_bf16)
-    hipLaunchKernelGGL((sgd_kernel<bf16, true, OptExt>), dim3(grid),
-                       dim3(kBlock), 0, s, (bf16*)p, (bf16*)g, m, n, lr,
-                       momentum, wd, zero_after, e);
-  else
-    hipLaunchKernelGGL((sgd_kernel<float, true, OptExt>), dim3(grid),
-                       dim3(kBlock), 0, s, (float*)p, (float*)g, m, n, lr,
-                       momentum, wd, zero_after, e);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((sgd_kernel<T, true, OptExt>), dim3(grid), dim3(kBlock),
+                       0, s, (T*)p, (T*)g, m, n, lr, momentum, wd, zero_after,
+                       e);
+  });
 }
 
 void launch_adam_ext(bool is_bf16, void* p, void* g, float* m, float* v,
@@ -337,25 +317,22 @@ void launch_adam_ext(bool is_bf16, void* p, void* g, float* m, float* v,
                      hipStream_t s) {
   const int grid = optim_grid(n);
   const OptExt e{clip_state, decoupled};
-  if (is_bf16)
-    hipLaunchKernelGGL((adam_kernel<bf16, true, OptExt>), dim3(grid),
-                       dim3(kBlock), 0, s, (bf16*)p, (bf16*)g, m, v, n, lr, b1,
-                       b2, eps, wd, inv_bc1, inv_sqrt_bc2, zero_after, e);
-  else
-    hipLaunchKernelGGL((adam_kernel<float, true, OptExt>), dim3(grid),
-                       dim3(kBlock), 0, s, (float*)p, (float*)g, m, v, n, lr,
-                       b1, b2, eps, wd, inv_bc1, inv_sqrt_bc2, zero_after, e);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((adam_kernel<T, true, OptExt>), dim3(grid), dim3(kBlock),
+                       0, s, (T*)p, (T*)g, m, v, n, lr, b1, b2, eps, wd,
+                       inv_bc1, inv_sqrt_bc2, zero_after, e);
+  });
 }
 
 int launch_grad_sumsq(bool is_bf16, const void* g, long long n,
                       float* partials, hipStream_t s) {
   const int grid = optim_grid(n);
-  if (is_bf16)
-    hipLaunchKernelGGL(grad_sumsq_kernel<bf16>, dim3(grid), dim3(kBlock), 0, s,
-                       (const bf16*)g, n, partials);
-  else
-    hipLaunchKernelGGL(grad_sumsq_kernel<float>, dim3(grid), dim3(kBlock), 0, s,
-                       (const float*)g, n, partials);
+  dispatch_dtype(is_bf16, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(grad_sumsq_kernel<T>, dim3(grid), dim3(kBlock), 0, s,
+                       (const T*)g, n, partials);
+  });
   return grid;
 }
 

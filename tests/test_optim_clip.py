@@ -66,10 +66,18 @@ coef == 1.0f against the dense op, an fp32 EXT step against the dense op fed
 torch's fp32 coef * g, a skipped step against the untouched inputs, a graph
 replay against the eager optimizer.
 
+The step checks run at n = 10007 and, in the *_flat_sizes tests, over
+step_sizes(V): n in {1, V - 1, V, V + 1, 255 V + 3, 256 V + 1, 4194333}, the
+flat shapes of the other exact tests: nothing but a tail, exactly one vector,
+a vector and a tail, one block with a partly filled last wave, two blocks, and
+a size past the capped grid (2048 blocks of 256 threads), where a thread takes
+a second vector and there is a tail. The bounds are per element, so they do
+not depend on n.
+
 The unmarked emulation test runs the same arithmetic in numpy (fp32 chains,
-the 6 shuffle levels, the 4 waves, the fp64 finalize, the fp32 step): honest
-arithmetic stays within 1.0 of every bound on every case, and each single
-defect exceeds 4x on the input chosen for it.
+the 6 shuffle levels, the 4 waves, the fp64 finalize, the fp32 SGD and Adam
+steps) over the same sizes: honest arithmetic stays within 1.0 of every bound
+on every case, and each single defect exceeds 4x on the input chosen for it.
 
 Figures measured on an MI355X (records, not thresholds) are in
 profiles/r09_grad_clip.md."""
@@ -115,6 +123,10 @@ def norm_sizes(V):
     return [1, V - 1, V, 256 * V, 256 * V + 1, 10007, 2048 * 256 * V + V + 1]
 
 
+def step_sizes(V):
+    return [1, V - 1, V, V + 1, 255 * V + 3, 256 * V + 1, 4194333]
+
+
 @functools.lru_cache(maxsize=None)
 def make_input(n, dtype, scale=1.0):
     """Unit-variance data (times scale) on the CPU, |x| = 16 scale planted at
@@ -144,7 +156,8 @@ def f32(x):
 
 
 def fma32(a, b, c):
-    return (np.float64(a) * np.float64(b) + np.float64(c)).astype(np.float32)
+    a, b, c = (np.asarray(t, np.float64) for t in (a, b, c))
+    return (a * b + c).astype(np.float32)
 
 
 def bf16_round(x):
@@ -234,9 +247,31 @@ def emu_sgd(p0, g, m0, lr, mu, wd, state, bf16, coef_after_wd=False,
     return (bf16_round(p) if bf16 else p), mom
 
 
+def emu_adam(p0, g, m0, v0, lr, b1, b2, eps, wd, bc1, bc2, coef, bf16,
+             decoupled):
+    """adam_kernel<T, EXT> on a finite step; returns p."""
+    p0, g, m0, v0 = f32(p0), f32(g), f32(m0), f32(v0)
+    lr, b1, b2, eps, wd = (np.float32(a) for a in (lr, b1, b2, eps, wd))
+    s = np.float32(1.0 / bc1)
+    r = np.float32(1.0 / math.sqrt(bc2))
+    one = np.float32(1.0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        gc = np.float32(coef) * g
+        if decoupled:
+            p0 = fma32(-lr * wd, p0, p0)
+            grad = gc
+        else:
+            grad = fma32(wd, p0, gc)
+        m = fma32(b1, m0, (one - b1) * grad)
+        v = fma32(b2, v0, (one - b2) * grad * grad)
+        denom = fma32(np.sqrt(v), r, eps)
+        p = fma32(-lr * s, m / denom, p0)
+    return bf16_round(p) if bf16 else p
+
+
 def sgd_ratio(p, p0, g, m0, lr, mu, wd, coef, u):
     """max |p - ref| / bound of the SGD step against float64."""
-    p0, g, m0 = (np.float64(a) for a in (p0, g, m0))
+    p0, g, m0 = (np.asarray(a, np.float64) for a in (p0, g, m0))
     lr, mu, wd = (float(np.float32(a)) for a in (lr, mu, wd))
     cg = float(coef) * g
     ref = p0 - lr * (mu * m0 + cg + wd * p0)
@@ -248,7 +283,7 @@ def sgd_ratio(p, p0, g, m0, lr, mu, wd, coef, u):
 def adam_ratio(p, p0, g, m0, v0, lr, b1, b2, eps, wd, bc1, bc2, coef, u,
                decoupled):
     """max |p - ref| / bound of the Adam / AdamW step (module docstring)."""
-    p0, g, m0, v0 = (np.float64(a) for a in (p0, g, m0, v0))
+    p0, g, m0, v0 = (np.asarray(a, np.float64) for a in (p0, g, m0, v0))
     lr, b1, b2, eps, wd = (float(np.float32(a)) for a in (lr, b1, b2, eps, wd))
     s = float(np.float32(1.0 / bc1))
     r = float(np.float32(1.0 / math.sqrt(bc2)))
@@ -315,7 +350,9 @@ def test_emulated_reduction_meets_the_bounds():
     print(f"emu worst: norm {worst_n:.3f} coef {worst_c:.3f}")
 
 
+@functools.lru_cache(maxsize=None)
 def _step_case(dtype, n=1031):
+    """(p0, g, m0, v0) as fp32 numpy arrays. Shared; never modified."""
     gen = torch.Generator().manual_seed(7)
     p0 = torch.randn(n, generator=gen).to(dtype).float().numpy()
     g = make_input(n, dtype).float().numpy()
@@ -326,16 +363,30 @@ def _step_case(dtype, n=1031):
 
 def test_emulated_step_meets_the_bound():
     lr, mu, wd = 0.1, 0.9, 0.1
+    h = ADAM_HP
+    worst = 0.0
     for bf16, u in ((False, 2.0 ** -23), (True, 2.0 ** -8)):
         dtype = torch.bfloat16 if bf16 else torch.float32
-        p0, g, m0, _ = _step_case(dtype)
-        x = torch.from_numpy(g)
-        st = emu_finalize([emu_partials(g, VEC[dtype])], 0.5 * ref_norm(x))
-        assert 0.4 < st[1] < 0.6
-        p, m = emu_sgd(p0, g, m0, lr, mu, wd, st, bf16)
-        r = sgd_ratio(p, p0, g, m0, lr, mu, wd, st[1], u)
-        print(f"emu sgd bf16={bf16}: p {r:.3f}")
-        assert r <= 1.0
+        for n in [1031] + step_sizes(VEC[dtype]):
+            p0, g, m0, v0 = _step_case(dtype, n)
+            x = torch.from_numpy(g)
+            st = emu_finalize([emu_partials(g, VEC[dtype])],
+                              0.5 * ref_norm(x))
+            assert 0.4 < st[1] < 0.6
+            p, m = emu_sgd(p0, g, m0, lr, mu, wd, st, bf16)
+            rs = [sgd_ratio(p, p0, g, m0, lr, mu, wd, st[1], u)]
+            for decoupled in (False, True):
+                p = emu_adam(p0, g, m0, v0, h["lr"], h["beta1"], h["beta2"],
+                             h["eps"], h["weight_decay"], h["bc1"], h["bc2"],
+                             st[1], bf16, decoupled)
+                rs.append(adam_ratio(p, p0, g, m0, v0, h["lr"], h["beta1"],
+                                     h["beta2"], h["eps"], h["weight_decay"],
+                                     h["bc1"], h["bc2"], st[1], u, decoupled))
+            print(f"emu bf16={bf16} n={n}: sgd {rs[0]:.3f} adam {rs[1]:.3f} "
+                  f"adamw {rs[2]:.3f}")
+            worst = max(worst, *rs)
+            assert max(rs) <= 1.0
+    print(f"emu step worst: {worst:.3f}")
 
 
 def test_single_defects_exceed_4x():
@@ -630,8 +681,8 @@ ADAM_HP = dict(lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.1,
 N_STEP = 10007
 
 
-def step_inputs(dtype, g_cpu=None):
-    p0, g, m0, v0 = _step_case(dtype, N_STEP)
+def step_inputs(dtype, g_cpu=None, n=N_STEP):
+    p0, g, m0, v0 = _step_case(dtype, n)
     t = lambda a, dt: torch.from_numpy(a).to(dt).to(DEV)
     g = t(g, dtype) if g_cpu is None else g_cpu.to(DEV)
     return t(p0, dtype), g, t(m0, torch.float32), t(v0, torch.float32)
@@ -651,13 +702,8 @@ def run_step(ops, opt, tensors, zero, ext, state=None, decoupled=False):
     return p, g, m, v
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
-@pytest.mark.parametrize("opt", ["sgd", "adam"])
-@pytest.mark.parametrize("zero", [False, True], ids=["keep_g", "zero_g"])
-def test_ext_step_with_coef_one_is_the_dense_step(dtype, opt, zero):
-    ops = require_hip()
-    tensors = step_inputs(dtype)
+def check_ext_step_with_coef_one(ops, dtype, opt, zero, n):
+    tensors = step_inputs(dtype, n=n)
     st = measure(ops, [tensors[1]], math.inf)
     assert st[1].item() == 1.0
     dense = run_step(ops, opt, tensors, zero, ext=False)
@@ -669,10 +715,26 @@ def test_ext_step_with_coef_one_is_the_dense_step(dtype, opt, zero):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
 @pytest.mark.parametrize("opt", ["sgd", "adam"])
-def test_fp32_clipped_step_is_the_dense_step_on_coef_g(opt):
+@pytest.mark.parametrize("zero", [False, True], ids=["keep_g", "zero_g"])
+def test_ext_step_with_coef_one_is_the_dense_step(dtype, opt, zero):
+    check_ext_step_with_coef_one(require_hip(), dtype, opt, zero, N_STEP)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
+@pytest.mark.parametrize("which", range(7))
+def test_ext_step_with_coef_one_flat_sizes(dtype, which):
     ops = require_hip()
-    tensors = step_inputs(torch.float32)
+    n = step_sizes(VEC[dtype])[which]
+    for opt in ("sgd", "adam"):
+        for zero in (False, True):
+            check_ext_step_with_coef_one(ops, dtype, opt, zero, n)
+
+
+def check_fp32_clipped_step(ops, opt, n):
+    tensors = step_inputs(torch.float32, n=n)
     st = measure(ops, [tensors[1]], 0.5 * ref_norm(tensors[1].cpu()))
     assert 0.4 < st[1].item() < 0.6
     out = run_step(ops, opt, tensors, False, ext=True, state=st)
@@ -685,9 +747,20 @@ def test_fp32_clipped_step_is_the_dense_step_on_coef_g(opt):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("opt", ["sgd", "adam"])
-def test_bf16_clipped_step_against_float64(opt):
+def test_fp32_clipped_step_is_the_dense_step_on_coef_g(opt):
+    check_fp32_clipped_step(require_hip(), opt, N_STEP)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", range(7))
+def test_fp32_clipped_step_flat_sizes(which):
     ops = require_hip()
-    tensors = step_inputs(torch.bfloat16)
+    for opt in ("sgd", "adam"):
+        check_fp32_clipped_step(ops, opt, step_sizes(4)[which])
+
+
+def check_bf16_clipped_step(ops, opt, n):
+    tensors = step_inputs(torch.bfloat16, n=n)
     st = measure(ops, [tensors[1]], 0.5 * ref_norm(tensors[1].cpu()))
     coef = st[1].item()
     assert 0.4 < coef < 0.6
@@ -702,16 +775,26 @@ def test_bf16_clipped_step_against_float64(opt):
         r = adam_ratio(p, p0, g, m0, v0, h["lr"], h["beta1"], h["beta2"],
                        h["eps"], h["weight_decay"], h["bc1"], h["bc2"], coef,
                        2.0 ** -8, decoupled=False)
-    print(f"bf16 clipped {opt}: p {r:.3f} of the bound")
+    print(f"bf16 clipped {opt} n={n}: p {r:.3f} of the bound")
     assert r <= 1.0
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("opt", ["sgd", "adam"])
-@pytest.mark.parametrize("clip", [False, True], ids=["noclip", "clip"])
-def test_fp32_decoupled_step_against_float64(opt, clip):
+def test_bf16_clipped_step_against_float64(opt):
+    check_bf16_clipped_step(require_hip(), opt, N_STEP)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", range(7))
+def test_bf16_clipped_step_flat_sizes(which):
     ops = require_hip()
-    tensors = step_inputs(torch.float32)
+    for opt in ("sgd", "adam"):
+        check_bf16_clipped_step(ops, opt, step_sizes(8)[which])
+
+
+def check_fp32_decoupled_step(ops, opt, clip, n):
+    tensors = step_inputs(torch.float32, n=n)
     st, coef = None, 1.0
     if clip:
         st = measure(ops, [tensors[1]], 0.5 * ref_norm(tensors[1].cpu()))
@@ -724,7 +807,7 @@ def test_fp32_decoupled_step_against_float64(opt, clip):
         # p' = p0 (1 - lr wd), then the chain of the SGD bound without wd
         lr, mu, wd = (float(np.float32(SGD_HP[k]))
                       for k in ("lr", "momentum", "weight_decay"))
-        p064, g64, m64 = (np.float64(a) for a in (p0, g, m0))
+        p064, g64, m64 = (np.asarray(a, np.float64) for a in (p0, g, m0))
         ref = p064 * (1 - lr * wd) - lr * (mu * m64 + coef * g64)
         bound = u * np.abs(ref) + 3 * E * lr * (np.abs(coef * g64)
                                                 + wd * np.abs(p064)
@@ -735,24 +818,34 @@ def test_fp32_decoupled_step_against_float64(opt, clip):
         r = adam_ratio(p, p0, g, m0, v0, h["lr"], h["beta1"], h["beta2"],
                        h["eps"], h["weight_decay"], h["bc1"], h["bc2"], coef, u,
                        decoupled=True)
-    print(f"fp32 decoupled {opt} clip={clip}: p {r:.3f} of the bound")
+    print(f"fp32 decoupled {opt} clip={clip} n={n}: p {r:.3f} of the bound")
     assert r <= 1.0
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
-@pytest.mark.parametrize("bad", ["inf_last_tail", "nan_first_vector"])
-@pytest.mark.parametrize("zero", [False, True], ids=["keep_g", "zero_g"])
-def test_non_finite_step_is_skipped(dtype, bad, zero):
+@pytest.mark.parametrize("opt", ["sgd", "adam"])
+@pytest.mark.parametrize("clip", [False, True], ids=["noclip", "clip"])
+def test_fp32_decoupled_step_against_float64(opt, clip):
+    check_fp32_decoupled_step(require_hip(), opt, clip, N_STEP)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", range(7))
+def test_fp32_decoupled_step_flat_sizes(which):
     ops = require_hip()
-    assert N_STEP % VEC[dtype]                      # there is a tail
-    x = make_input(N_STEP, dtype).clone()
+    for opt in ("sgd", "adam"):
+        for clip in (False, True):
+            check_fp32_decoupled_step(ops, opt, clip, step_sizes(4)[which])
+
+
+def check_non_finite_step_is_skipped(ops, dtype, bad, zero, n):
+    x = make_input(n, dtype).clone()
     if bad == "inf_last_tail":
         x[-1] = math.inf
     else:
-        x[1] = math.nan
-    tensors = step_inputs(dtype, x)
-    good = step_inputs(dtype)
+        x[min(1, n - 1)] = math.nan
+    tensors = step_inputs(dtype, x, n=n)
+    good = step_inputs(dtype, n=n)
     for opt in ("sgd", "adam"):
         st = torch.tensor([0.0, 1.0, 1.0, 2.0], device=DEV)
         measure(ops, [tensors[1]], 1.0, st)
@@ -771,6 +864,26 @@ def test_non_finite_step_is_skipped(dtype, bad, zero):
         for a, b in zip(run_step(ops, opt, after, zero, ext=True, state=st),
                         run_step(ops, opt, after, zero, ext=False)):
             assert same_bits(a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
+@pytest.mark.parametrize("bad", ["inf_last_tail", "nan_first_vector"])
+@pytest.mark.parametrize("zero", [False, True], ids=["keep_g", "zero_g"])
+def test_non_finite_step_is_skipped(dtype, bad, zero):
+    assert N_STEP % VEC[dtype]                      # there is a tail
+    check_non_finite_step_is_skipped(require_hip(), dtype, bad, zero, N_STEP)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
+@pytest.mark.parametrize("which", range(7))
+def test_non_finite_step_is_skipped_flat_sizes(dtype, which):
+    ops = require_hip()
+    n = step_sizes(VEC[dtype])[which]
+    for bad in ("inf_last_tail", "nan_first_vector"):
+        for zero in (False, True):
+            check_non_finite_step_is_skipped(ops, dtype, bad, zero, n)
 
 
 @pytest.mark.gpu
